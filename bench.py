@@ -17,6 +17,7 @@ Workloads (`--workload`):
                   step = encode of the shard + the gather (gather_ms reported separately).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg4|cfg5] [--rows R]
+                  [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N, or plain
          `python bench.py --gpus N`: with no RANK in the environment the script starts that launcher
          itself as a child process (before any GPU call) and exits with its code.
@@ -26,9 +27,20 @@ Workloads (`--workload`):
 
 Rows are packed UTF-8 + int64 offsets already resident in HBM when the timed region starts. Prints
 ONE JSON line (rank 0): value = whole-job MB/s of raw UTF-8 input (max-over-ranks time), tokens/s,
-the dominant kernel's HBM roofline (SURVEY.md §8(d) read bytes / its average launch time from HIP
-events on the encode stream; PMC traffic from profiles/), the CPU baseline (the oracle, 1 thread
-and all host cores, on a bounded sample) and end-to-end host->host rates (N = 1 only).
+ms_per_step and the dominant kernel's HBM roofline (SURVEY.md §8(d) read bytes / its average launch
+time from the HIP events of the timed steps themselves; PMC traffic from profiles/). A plain run does
+nothing else: set up, warm up, time --steps steps, write the outputs (--dump-outputs), print.
+
+--full adds every measurement that takes runs of its own (N = 1 only; each has its --no-* switch):
+the per-pass cycle split of the tile kernel (one extra step with the pass clocks on), the cfg5
+SentencePiece launch block, the config 2/3/5 side measurements, the end-to-end host->host rates,
+the per-call latency block and the CPU baseline (the oracle, 1 thread and all host cores, on a
+bounded sample).
+
+--dump-outputs DIR: after the timed steps, what the LAST timed step returned to its caller (the id
+stream and the row offsets into it; every rank its own shard's, as <name>_rank<k>.npy when N > 1)
+goes to DIR as .npy files (dump_outputs below). The inputs are generated from a fixed seed, so two
+builds run with the same arguments can be compared file for file.
 """
 import argparse
 import glob
@@ -70,6 +82,10 @@ def parse():
     ap.add_argument("--no-others", action="store_true", help="skip the config 2/3/5 side measurements")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end host->host rates")
     ap.add_argument("--no-single", action="store_true", help="skip the per-call latency block")
+    ap.add_argument("--full", action="store_true", help="also run every side measurement (pass-clock step, cfg5 launch "
+                    "block, side configs, end to end, per-call latency, CPU baseline); off: only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs "
+                    "(ids, row offsets) to DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -413,6 +429,44 @@ def cfg5_block(args, dev):
     return res
 
 
+# ------------------------------------------------------------------------------------------ outputs
+DUMP_MAX_IDS = 12_000_000   # float32 ids: 48 MB
+DUMP_MAX_ROWS = 1_000_000   # float64 row numbers + offsets: 16 MB
+
+
+def dump_outputs(path, ids, oo, suffix=""):
+    """What the last timed step returned (ids: the id stream, oo: rows + 1 offsets into it) as
+    path/<name><suffix>.npy, under 64 MB in all:
+      totals   float64 [rows, ids] of the WHOLE output
+      rows     float64 the row numbers written (every row if the output is small enough, else a
+               fixed seeded sample, ascending)
+      offsets  float64 len(rows) + 1 offsets into `ids` below
+      ids      float32 the ids of those rows, row after row (every id < 2^24 is exact in float32)
+    """
+    os.makedirs(path, exist_ok=True)
+    n = int(oo.numel()) - 1
+    h_oo = oo.cpu().numpy().astype(np.int64)
+    n_ids = int(h_oo[-1]) if n >= 0 else 0
+    if n <= DUMP_MAX_ROWS and n_ids <= DUMP_MAX_IDS:
+        sel = np.arange(n, dtype=np.int64)
+        sub_offs = h_oo
+        sub_ids = ids[:n_ids].cpu().numpy()
+    else:
+        sel = np.random.RandomState(SEED).permutation(n)[:min(n, DUMP_MAX_ROWS)].astype(np.int64)
+        lens = h_oo[sel + 1] - h_oo[sel]
+        keep = int(np.searchsorted(np.cumsum(lens), DUMP_MAX_IDS, side="right"))  # a prefix of the permutation
+        sel = np.sort(sel[:keep])
+        lens = h_oo[sel + 1] - h_oo[sel]
+        sub_offs = np.zeros(len(sel) + 1, dtype=np.int64)
+        np.cumsum(lens, out=sub_offs[1:])
+        # position j of row i of the sample is id h_oo[sel[i]] + j of the stream
+        idx = np.arange(int(sub_offs[-1]), dtype=np.int64) + np.repeat(h_oo[sel] - sub_offs[:-1], lens)
+        sub_ids = ids[torch.from_numpy(idx).to(ids.device)].cpu().numpy()
+    for name, arr, dt in (("totals", np.array([n, n_ids]), np.float64), ("rows", sel, np.float64),
+                          ("offsets", sub_offs, np.float64), ("ids", sub_ids, np.float32)):
+        np.save(os.path.join(path, name + suffix + ".npy"), np.asarray(arr).astype(dt))
+
+
 # ------------------------------------------------------------------------------------------ launcher
 def launch_workers(args):
     """`--gpus N` (N > 1) without a launcher: run torch.distributed.run with N ranks on this node as
@@ -571,7 +625,11 @@ def main():
     engine.profile_enable(False)
     fb_rows = engine.fallback_rows(local)
     ptc = {}
-    passes = pass_split(engine, step, local, ptc) if world == 1 else {}  # step() of N > 1 holds a collective
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ids, oo, "" if world == 1 else "_rank%d" % rank)
+        log(rank, "outputs written")
+    # step() of N > 1 holds a collective
+    passes = pass_split(engine, step, local, ptc) if world == 1 and args.full else {}
 
     if dist:
         t = torch.tensor([elapsed, gather_s[0]], dtype=torch.float64, device=cdev)
@@ -604,19 +662,20 @@ def main():
         roofline["pretoken_cache"] = ptc
 
     others = e2e = cpu = c5 = single = None
-    if rank == 0 and world == 1 and not cfg5 and not args.no_cfg5:
+    side = rank == 0 and world == 1 and args.full  # everything below takes runs of its own
+    if side and not cfg5 and not args.no_cfg5:
         log(rank, "cfg5 launch block")
         c5 = cfg5_block(args, local)
-    if rank == 0 and world == 1 and not args.no_others:
+    if side and not args.no_others:
         log(rank, "other configs")
         others = other_configs(local)
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if side and not args.no_e2e:
         log(rank, "end to end")
         e2e = end_to_end(local, model, buf, offs, kind)
-    if rank == 0 and world == 1 and not args.no_single:
+    if side and not args.no_single:
         log(rank, "per-call latency")
         single = single_call(local)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if side and not args.no_cpu:
         log(rank, "timed region done (%.1f ms/step); CPU baseline" % ms_step)
         cpu = cpu_baseline(args, buf, offs, kind)
 

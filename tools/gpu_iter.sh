@@ -35,6 +35,6 @@ if [ -n "${AB_VARIANTS-}" ]; then
   cat $OUT/ab.jsonl
 fi
 if [ "${BENCH-none}" != "none" ]; then
-  timeout -k 10 600 python -u bench.py $BENCH > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 600 python -u bench.py --full $BENCH > $OUT/bench.json 2> $OUT/bench.err
   tail -c 300 $OUT/bench.json
 fi

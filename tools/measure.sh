@@ -1,7 +1,7 @@
 #!/bin/bash
 # The round's measurement set on the GPU box, each step under its own time limit, chained by set -e:
 #   tests    the whole GPU suite                         smoke   __graft_entry__.smoke()
-#   bench    the default bench line (cfg4 + cfg5 block + side configs + per-call latency + CPU baseline)
+#   bench    the bench --full line (cfg4 + cfg5 block + side configs + per-call latency + CPU baseline)
 #   nccl     bench --workload cfg5 under torchrun (nccl, world 1)
 #   trace    rocprofv3 kernel trace + stats of the cfg4 bench command
 #   pmc      PMC passes over the cfg4 (10 M-row BPE) and cfg5 (25 M-row SPM) launch shapes (tools/pmc_op.sh)
@@ -22,13 +22,13 @@ for s in $STEPS; do
            tail -1 $OUT/gpu_tests.log ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1
            tail -1 $OUT/smoke.log ;;
-    bench) timeout -k 10 700 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+    bench) timeout -k 10 700 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
            tail -c 300 $OUT/bench.json ;;
     nccl) timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-            --master-port 29513 bench.py --workload cfg5 --steps 3 --warmup 1 --no-cpu --no-e2e --no-others --no-single \
+            --master-port 29513 bench.py --full --workload cfg5 --steps 3 --warmup 1 --no-cpu --no-e2e --no-others --no-single \
             > $OUT/bench_cfg5_nccl_w1.json 2> $OUT/bench_cfg5_nccl_w1.err ;;
     trace) timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace --output-format csv -- \
-             python3 bench.py --no-cpu --no-e2e --no-others --no-single --steps 5 > $OUT/trace.log 2>&1 ;;
+             python3 bench.py --full --no-cpu --no-e2e --no-others --no-single --steps 5 > $OUT/trace.log 2>&1 ;;
     pmc) bash tools/pmc_op.sh $OUT/pmc_cfg4 bpe 10000000
          bash tools/pmc_op.sh $OUT/pmc_cfg5 spm 25000000 ;;
     pmcrows) bash tools/pmc_op.sh $OUT/pmc_cfg2 segment3 1000000 0
