@@ -15,11 +15,19 @@
  *    only enqueue work: results are valid after the stream is synchronized.
  *  - Input: `in` holds offs[n] bytes (offs[0] == 0, offs non-decreasing). Each row is one string
  *    of the reference API. The buffer must stay readable through offs[n] rounded up to 16 bytes (rows are
- *    read in aligned 16-byte blocks).
+ *    read in aligned 16-byte blocks). `in` needs no alignment: it may point anywhere into a larger
+ *    allocation (a sub-range of another batch), and what precedes it is never taken for row text. The
+ *    bytes after offs[n] may hold anything: they are loaded with the last block but never decoded,
+ *    so the last row ends at offs[n] whatever follows it (a combining mark, a UTF-8 lead byte, ...).
+ *    The same holds for the ids of the decode calls.
  *  - Output sizing: callers pass a capacity `cap` (elements). out_offs[0..n] is always written;
  *    the total is out_offs[n]. If out_offs[n] > cap, the call still returns AK_OK but the output
  *    elements are incomplete: re-run with cap >= out_offs[n] (the bound helpers below give caps
- *    that are always sufficient).
+ *    that are always sufficient). Nothing is stored at or past element `cap` of an output array
+ *    (cap == out_offs[n] exactly is enough, cap == 0 is allowed), past out_offs[n] or past
+ *    row_status[n - 1]; out_offs and row_status are complete at any capacity. A short capacity is
+ *    the caller's matter, not an engine overflow: ak_ws_check() still returns AK_OK after such a
+ *    call, and the workspace keeps no state from it (the re-run may use the same workspace).
  *  - row_status (optional, u8[n], may be NULL): bit 0 = row had invalid UTF-8 (decoded as U+FFFD
  *    per byte). Bit 2 (AK_ROW_LIMIT) is only ever set together with an engine-bug error from
  *    ak_ws_check(): no row length is rejected (see "Row lengths").
@@ -93,7 +101,7 @@ void ak_ws_free(ak_ws *ws);
 int ak_ws_set_tiling(ak_ws *ws, int bpe_path, int tile_rows);
 /* Synchronous health check after a batch: AK_ERR_HIP if the last call flagged an internal
  * overflow (a row producing more output than its staging slot bound, or overflowing the huge
- * tier; never observed). */
+ * tier; never observed). A call whose `cap` was short of out_offs[n] flags nothing: AK_OK. */
 int ak_ws_check(ak_ws *ws);
 
 /* Replaces Tokenizer.from_file(path) (tokenizer.py:96-97) for the model cli.py:276-299 trains:

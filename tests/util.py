@@ -38,6 +38,71 @@ SEG_KEYS = ((3, False, "ak"), (3, True, "ak_m"), (-1, False, "ak_raw"), (-1, Tru
 SW_KEYS = ((3, "sw"), (-1, "sw_raw"))
 
 
+BUFFER_UNIT = 64          # rows per tile work unit (ak_tile.h TILE_UNIT)
+BUFFER_GUARD = 4096       # guard elements after every output array of the buffer-contract tests
+BUFFER_BAD_ROWS = (b"a\x80b", b"\xe0\xa4")
+
+
+def buffer_batch():
+    """The 229-row batch of the buffer-contract tests (tests/test_gpu_buffers.py and its host mirror
+    tests/test_emu_buffers.py) as a list of UTF-8 byte rows: three full 64-row units and one of 37.
+    Unit 0 and unit 2 are synthetic Hinglish only (no fallback row: the streaming unit copy); units 1
+    and 3 carry, between synthetic rows, the rows that drive every other emit path; the huge-tier row
+    is the last row of the last unit, so the end of every output and the slack after the input belong
+    to a non-trivial row."""
+    from akshar_amd import synth
+    # empty; one under the 480-byte tile buffer limit; over the 768-byte one (one lane per row); NA +
+    # nukta + AA (NFC composes); invalid UTF-8; the slow tier; precomposed nukta letters (normalize
+    # expands each from 3 to 6 bytes); a nukta after a virama (NFC reorders: the tile kernels compose the
+    # rows above themselves, a reordering goes to the fallback waves)
+    unit1 = ["", "a" * 479, "x" * 769, "\u0928\u093c\u093e", BUFFER_BAD_ROWS[0], "x" * 5000,
+             "\u095b\u093f\u0902\u0926\u0917\u0940 \u095e\u093f\u0930", "\u0928\u094d\u093c\u093e yaar"]
+    # blank; at the tile buffer limit; a row of 64+ ids; e + acute, K / a with dot below + acute (NFC
+    # rows); a truncated sequence; an acute before a dot below (NFC reorders: the fallback waves)
+    unit3 = ["  ", "a" * 480, "a b " * 120, "cafe\u0301", "\u1e32\u0301x \u1ea1\u0301b", BUFFER_BAD_ROWS[1],
+             "a\u0301\u0323 b"]
+    n = 3 * BUFFER_UNIT + 37
+    rows = [None] * n
+    for base, special in ((BUFFER_UNIT, unit1), (3 * BUFFER_UNIT, unit3)):
+        for k, s in enumerate(special):
+            rows[base + 2 + 5 * k] = s
+    rows[n - 1] = "ab" * 2500
+    fill = iter(synth.lines(synth.KIND_HINGLISH, n - len(unit1) - len(unit3) - 1, seed=4242))
+    rows = [next(fill) if r is None else r for r in rows]
+    return [r if isinstance(r, bytes) else r.encode("utf-8") for r in rows]
+
+
+def pack_rows(rows):
+    """list[bytes] -> (u8 bytes, u64 offsets) as the oracle takes them."""
+    offs = np.zeros(len(rows) + 1, dtype=np.uint64)
+    np.cumsum([len(r) for r in rows], out=offs[1:])
+    return np.frombuffer(b"".join(rows) or b"\0", dtype=np.uint8).copy(), offs
+
+
+def buffer_capacities(oo, u8):
+    """Output capacities the buffer-contract tests run with, from the oracle's offsets `oo`: the exact
+    total, one short (u8 outputs: also two and three short, the tail of a dword store), one element
+    into the second unit and as many short of the first unit's end (the end of a streamed unit run,
+    where the batch's own end belongs to a unit copied row by row), 1 and 0."""
+    total, unit = int(oo[-1]), int(oo[BUFFER_UNIT])
+    short = (1, 2, 3) if u8 else (1,)
+    caps = [total] + [total - k for k in short] + [unit + 1] + [unit - k for k in short] + [1, 0]
+    assert all(0 <= c <= total for c in caps) and 3 < unit - 3 and unit + 1 < total - 3
+    return caps
+
+
+def oracle_bad_rows(buf, offs):
+    """u8[n]: 1 where the oracle's UTF-8 decoder met an invalid byte (row_status bit 0)."""
+    from oracle import oracle as O
+    n = len(offs) - 1
+    bad = np.zeros(max(n, 1), dtype=np.uint8)
+    out = np.zeros(int(offs[-1]) * 3 + 16, dtype=np.uint8)
+    oo = np.zeros(n + 1, dtype=np.uint64)
+    O.lib().or_normalize(0, buf.ctypes.data, offs.ctypes.data, n, out.ctypes.data, len(out), oo.ctypes.data,
+                         bad.ctypes.data)
+    return bad[:n]
+
+
 def tiny_bpe_model(path):
     """A 43-token BPE model where two vocab strings are NOT their own merge_all result:
     "abc" (merges b c -> bc before a b -> ab, and no a bc merge: [a, bc]) and "cab" ([c, ab])."""
