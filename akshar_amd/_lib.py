@@ -24,6 +24,11 @@ AK_ST_NFC = 1
 AK_ST_LOWER = 2
 AK_ST_FILTER = 4
 AK_ST_ELONG = 8
+# ak_ids_pad / ak_ids_pack flags
+AK_PAD_LEFT = 1
+AK_TRUNC_LEFT = 2
+AK_DENSE_I64 = 4
+AK_PACK_DROP_LAST = 8
 AK_ROW_BAD_UTF8 = 1
 AK_ROW_LIMIT = 4
 AK_TILE_PASSES = ("pre", "stage_decode_nfc_map", "elong_ws_pretok", "pretoken_cache", "pretoken_starts", "merge_or_viterbi",
@@ -77,6 +82,9 @@ SIGNATURES = {
     "ak_spm_cache_info": (I32, [P, ctypes.POINTER(U64)]),
     "ak_ws_fallback_rows": (I32, [P, ctypes.POINTER(U64), ctypes.POINTER(U64)]),
     "ak_ws_fallback_detail": (I32, [P, P]),
+    "ak_ids_pad": (I32, [P, P, U64, U32, ctypes.c_int32, U32, U32, I32, P, U64, P, P, P]),
+    "ak_ids_pack": (I32, [P, P, U64, U32, ctypes.c_int32, ctypes.c_int32, I32, P, P, P, U64, P]),
+    "ak_ids_pack_blocks": (U64, [U64, U64, I32, U32, I32]),
     "ak_normalize_cap": (U64, [U64, U64]),
     "ak_segment_cap": (U64, [U64, U64]),
     "ak_bpe_encode_cap": (U64, [U64, U64]),

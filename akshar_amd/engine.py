@@ -477,8 +477,106 @@ class SPM:
         return out[:total], oo
 
 
+def _check_ids(ids, offs):
+    """Ragged id rows as the encode calls return them: int32 ids, int64 offsets (n + 1), contiguous, on
+    one device; returns n."""
+    if ids.dtype != torch.int32 or offs.dtype != torch.int64:
+        raise TypeError("id rows must be int32 ids with int64 offsets")
+    if not (ids.is_cuda and offs.is_cuda) or ids.device != offs.device:
+        raise TypeError("id rows must be device tensors on one device")
+    if not ids.is_contiguous() or not offs.is_contiguous():
+        raise TypeError("id rows must be contiguous")
+    n = offs.numel() - 1
+    if n < 0:
+        raise ValueError("offs must have n+1 entries")
+    return n
+
+
+def _check_dense(t, name, dtypes, numel, dev):
+    """A caller-provided output of pad_ids: dtype, device, contiguity and size, checked before the
+    launch because the kernel writes through it."""
+    if t.dtype not in dtypes or t.device != dev or not t.is_contiguous():
+        raise TypeError("%s must be a contiguous %s tensor on %s" % (name, " / ".join(str(d) for d in dtypes), dev))
+    if t.numel() != numel:
+        raise ValueError("%s must have %d elements, got %d" % (name, numel, t.numel()))
+
+
+def _side(name, v):
+    if v not in ("left", "right"):
+        raise ValueError("%s must be 'left' or 'right', got %r" % (name, v))
+    return v == "left"
+
+
+def _dense_dtype(dtype):
+    if dtype not in (torch.int32, torch.int64):
+        raise TypeError("dtype must be torch.int32 or torch.int64")
+    return _lib.AK_DENSE_I64 if dtype == torch.int64 else 0
+
+
+def pad_ids(ids, offs, width, pad_id, *, padding_side="right", truncation_side="right", keep_head=0, keep_tail=0,
+            dtype=torch.int32, out=None, mask=None, lengths=None):
+    """Ragged device id rows -> (input_ids [n, width], attention_mask bool [n, width], lengths int32 [n])
+    on the device, in one launch on the current stream (include/akshar.h ak_ids_pad): rows longer than
+    `width` are truncated keeping their first keep_head and last keep_tail ids (a template's special
+    tokens) and the first (truncation_side "right") or last ("left") ids between; the others are padded
+    with pad_id on padding_side. out / mask / lengths (optional) receive the results in place."""
+    n = _check_ids(ids, offs)
+    dev = ids.device
+    width, keep_head, keep_tail = int(width), int(keep_head), int(keep_tail)
+    flags = _dense_dtype(dtype)
+    flags |= _lib.AK_PAD_LEFT if _side("padding_side", padding_side) else 0
+    flags |= _lib.AK_TRUNC_LEFT if _side("truncation_side", truncation_side) else 0
+    if width <= 0:
+        raise ValueError("width must be positive")
+    if keep_head < 0 or keep_tail < 0 or keep_head + keep_tail > width:
+        raise ValueError("keep_head + keep_tail must lie in 0..width")
+    if out is not None:
+        _check_dense(out, "out", (dtype,), n * width, dev)
+    if mask is not None:
+        _check_dense(mask, "mask", (torch.bool, torch.uint8), n * width, dev)
+    if lengths is not None:
+        _check_dense(lengths, "lengths", (torch.int32,), n, dev)
+    with torch.cuda.device(dev):
+        out = torch.empty((n, width), dtype=dtype, device=dev) if out is None else out
+        mask = torch.empty((n, width), dtype=torch.bool, device=dev) if mask is None else mask
+        lengths = torch.empty(n, dtype=torch.int32, device=dev) if lengths is None else lengths
+        if n:
+            src = ids if ids.numel() else torch.zeros(1, dtype=torch.int32, device=dev)  # all rows empty
+            check(_lib.lib().ak_ids_pad(_ptr(src), _ptr(offs), n, width, int(pad_id), keep_head, keep_tail, flags,
+                                        _ptr(out), n, _ptr(mask), _ptr(lengths), _stream(dev)), "ak_ids_pad")
+    return out.view(n, width), mask.view(n, width), lengths
+
+
+def pack_ids(ids, offs, block, *, sep_id=None, pad_id=0, drop_last=False, dtype=torch.int32, positions=True, docs=True):
+    """Ragged device id rows -> (input_ids [n_blocks, block], position_ids | None, doc_ids | None) on the
+    device, in one launch on the current stream (include/akshar.h ak_ids_pack): the rows concatenated,
+    each followed by sep_id if given, cut into blocks; the last block is padded with pad_id, or dropped
+    with drop_last. position_ids restart at every row and count on across blocks, doc_ids hold the row
+    index (padding: 0 and -1). `ids` must hold exactly the offs[-1] ids of the rows (as the encode calls
+    return them): the block count comes from ids.numel(), with no read-back."""
+    n = _check_ids(ids, offs)
+    dev = ids.device
+    block = int(block)
+    if block <= 0:
+        raise ValueError("block must be positive")
+    if sep_id is not None and int(sep_id) < 0:
+        raise ValueError("sep_id must be a token id (or None for no separator)")
+    flags = _dense_dtype(dtype) | (_lib.AK_PACK_DROP_LAST if drop_last else 0)
+    nb = int(_lib.lib().ak_ids_pack_blocks(ids.numel(), n, int(sep_id is not None), block, flags))
+    with torch.cuda.device(dev):
+        out = torch.empty((nb, block), dtype=dtype, device=dev)
+        pos = torch.empty((nb, block), dtype=torch.int32, device=dev) if positions else None
+        doc = torch.empty((nb, block), dtype=torch.int32, device=dev) if docs else None
+        if nb:
+            src = ids if ids.numel() else torch.zeros(1, dtype=torch.int32, device=dev)  # all rows empty
+            check(_lib.lib().ak_ids_pack(_ptr(src), _ptr(offs), n, block, -1 if sep_id is None else int(sep_id),
+                                         int(pad_id), flags, _ptr(out), _ptr(pos), _ptr(doc), nb, _stream(dev)),
+                  "ak_ids_pack")
+    return out, pos, doc
+
+
 __all__ = ["pack", "pack_host", "to_device", "normalize_batch", "segment_batch", "switches_batch", "BPE", "SPM",
-           "flags_of", "workspace", "AK_RAW"]
+           "flags_of", "workspace", "AK_RAW", "pad_ids", "pack_ids"]
 
 
 def profile_enable(on=True, passes=False):

@@ -62,6 +62,9 @@ class BPEModel:
         self.bos = int(st[ids[0]]["ids"][0])
         self.eos = int(st[ids[2]]["ids"][0])
         self.bos_token, self.eos_token = ids[0], ids[2]
+        # ids of "<pad>" / "</s>" for padded batches and packed blocks (None when the vocabulary has none)
+        self.pad_id = self.vocab.get("<pad>")
+        self.eos_id = self.vocab.get("</s>")
         # HF decode with no decoder configured: tokens joined by ' ' (special tokens skipped)
         self.special_ids = {int(a["id"]) for a in j.get("added_tokens", []) if a.get("special")}
         # AddedVocabulary: split the text on these before the normalizer (ak_bpe_set_added)
@@ -187,6 +190,9 @@ class SPMModel:
             raise NotImplementedError("only byte_fallback models are supported (cli.py:244)")
         self.vocab_size = len(pieces)
         self.piece_to_id = {p: i for i, p in enumerate(pieces)}
+        # ids of "<pad>" / "</s>" for padded batches and packed blocks (None when the model has none)
+        self.pad_id = self.piece_to_id.get(b"<pad>")
+        self.eos_id = self.piece_to_id.get(b"</s>")
         # Fast path precondition: no piece carries U+2581 after its first character, so every
         # '▁' is a forced Viterbi boundary (SPM kernel).
         self.ws_boundary = all(b"\xe2\x96\x81" not in p[1:] for p, t in zip(pieces, types)

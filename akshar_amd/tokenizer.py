@@ -82,6 +82,53 @@ class aksharTokenizer:
             raise ValueError("need model for IDs")
         return self.model.encode_batch(buf, offs, flags=self._flags, nbytes=nbytes)
 
+    def _encode_rows(self, texts):
+        """list[str] or a (buf, offs) device pair -> device (int32 ids, int64 row offsets)."""
+        if self.model is None:
+            raise ValueError("need model for IDs")
+        if isinstance(texts, tuple):
+            return self.encode_packed(*texts)
+        hb, ho = engine.pack_host(list(texts))
+        buf, offs = engine.to_device(hb, ho)
+        return self.encode_packed(buf, offs, nbytes=int(ho[-1]))
+
+    def _pad_id(self, pad_id):
+        pad_id = self.model.model.pad_id if pad_id is None else pad_id
+        if pad_id is None:
+            raise ValueError("the model has no <pad> token: pass pad_id")
+        return int(pad_id)
+
+    def encode_padded(self, texts, max_length: int, *, padding_side: str = "right", truncation_side: str = "right",
+                      pad_id: Optional[int] = None) -> dict:
+        """texts (list[str] or a (buf, offs) device pair) -> {"input_ids" [n, max_length],
+        "attention_mask" bool, "lengths" int32 [n]} as device tensors: HF tokenizers' enable_truncation
+        + enable_padding(length=max_length). BPE rows keep their <s> ... </s> through truncation (the
+        template is applied after it); pad_id defaults to the model's <pad>."""
+        if self.model is None:
+            raise ValueError("need model for IDs")
+        pad_id = self._pad_id(pad_id)
+        keep = 1 if self.model_type == "bpe" else 0
+        ids, oo = self._encode_rows(texts)
+        out, mask, lengths = engine.pad_ids(ids, oo, max_length, pad_id, padding_side=padding_side,
+                                            truncation_side=truncation_side, keep_head=keep, keep_tail=keep)
+        return {"input_ids": out, "attention_mask": mask, "lengths": lengths}
+
+    def encode_blocks(self, texts, block_size: int, *, sep_id=..., pad_id: Optional[int] = None,
+                      drop_last: bool = False) -> dict:
+        """texts (list[str] or a (buf, offs) device pair) -> {"input_ids" [n_blocks, block_size],
+        "position_ids", "doc_ids"} as device tensors: the rows' ids concatenated and cut into blocks
+        (LM pretraining's "group texts"), with each token's index inside its row and its row index so
+        attention can be kept inside documents. sep_id follows every row: by default the model's </s>
+        for SentencePiece and none for BPE (its rows end in </s> already); None for no separator."""
+        if self.model is None:
+            raise ValueError("need model for IDs")
+        pad_id = self._pad_id(pad_id)
+        if sep_id is ...:
+            sep_id = self.model.model.eos_id if self.model_type == "sentencepiece" else None
+        ids, oo = self._encode_rows(texts)
+        out, pos, doc = engine.pack_ids(ids, oo, block_size, sep_id=sep_id, pad_id=pad_id, drop_last=drop_last)
+        return {"input_ids": out, "position_ids": pos, "doc_ids": doc}
+
     def encode_batch(self, texts: List[str]) -> List[List[int]]:
         if self.model is None:
             raise ValueError("need model for IDs")

@@ -283,6 +283,44 @@ int ak_bpe_decode(const ak_bpe *m, ak_ws *ws, const uint32_t *ids, const uint64_
 int ak_spm_decode(const ak_spm *m, ak_ws *ws, const uint32_t *ids, const uint64_t *id_offs, uint64_t n, uint8_t *out,
                   uint64_t cap, uint64_t *out_offs, void *stream);
 
+/* Model-ready outputs from the ragged result of the encode calls (ids, id_offs[n+1] with id_offs[0] == 0,
+ * as ak_bpe_encode / ak_spm_encode write them; `ids` needs no alignment). Device pointers; each call
+ * is one kernel launch on `stream`, with no workspace and no read-back. Output arrays may be NULL
+ * where marked optional. n == 0 and a capacity of 0 are allowed and store nothing. Argument errors
+ * (NULL ids with n > 0, NULL id_offs, NULL out, width == 0 / block == 0, keep_head + keep_tail >
+ * width, a flag bit the call does not take) are AK_ERR_ARG, found on the host before any device work.
+ *
+ * ak_ids_pad: out[n x width] (int32, or int64 with AK_DENSE_I64), row-major; what HF tokenizers'
+ *   enable_truncation(width) + enable_padding(length=width, pad_id) give for a single-sequence template
+ *   of keep_head leading and keep_tail trailing special tokens ("<s> $A </s>": 1 and 1). With L a row's
+ *   length: L <= width keeps the row whole; L > width keeps its first keep_head ids, its last keep_tail
+ *   ids and width - keep_head - keep_tail of the ids between them, the first ones, or the last ones
+ *   with AK_TRUNC_LEFT. The other width - min(L, width) positions hold pad_id, after the ids, or before
+ *   them with AK_PAD_LEFT. mask (optional, u8[n x width]): 1 for an id, 0 for padding; lengths (optional,
+ *   int32[n]): min(L, width). An empty row is all padding. A row with 0 < L < keep_head + keep_tail is
+ *   kept whole if L <= width, otherwise truncated as if keep_head = keep_tail = 0 (it cannot be longer than
+ *   width, which is at least keep_head + keep_tail, so it is always kept whole). Nothing is stored at or
+ *   past row cap_rows of out, mask or lengths.
+ * ak_ids_pack: the rows concatenated, each followed by sep_id if sep_id >= 0 (S = 1, else S = 0), cut
+ *   into blocks of `block` elements: row r takes stream positions [id_offs[r] + r S, id_offs[r+1] +
+ *   (r+1) S), the total is T = id_offs[n] + n S, and out[n_blocks x block] (int32 / int64) has n_blocks =
+ *   ceil(T / block), the positions from T on holding pad_id, or floor(T / block) with
+ *   AK_PACK_DROP_LAST. pos (optional, int32, out's shape): the element's index inside its row (the
+ *   separator included), counting on across block boundaries; 0 for padding. doc (optional, int32):
+ *   the row index, -1 for padding; a row without elements (empty, S = 0) appears nowhere. Nothing is
+ *   stored at or past block cap_blocks of out, pos or doc. id_offs[n] is read on the device:
+ *   ak_ids_pack_blocks (host arithmetic) gives n_blocks for n_ids = id_offs[n] total ids. */
+#define AK_PAD_LEFT 1       /* ak_ids_pad: padding before the ids */
+#define AK_TRUNC_LEFT 2     /* ak_ids_pad: truncation keeps the last ids of the body */
+#define AK_DENSE_I64 4      /* both: out is int64 */
+#define AK_PACK_DROP_LAST 8 /* ak_ids_pack: no partial last block */
+int ak_ids_pad(const int32_t *ids, const uint64_t *id_offs, uint64_t n, uint32_t width, int32_t pad_id,
+               uint32_t keep_head, uint32_t keep_tail, int flags, void *out, uint64_t cap_rows, uint8_t *mask,
+               int32_t *lengths, void *stream);
+int ak_ids_pack(const int32_t *ids, const uint64_t *id_offs, uint64_t n, uint32_t block, int32_t sep_id,
+                int32_t pad_id, int flags, void *out, int32_t *pos, int32_t *doc, uint64_t cap_blocks, void *stream);
+uint64_t ak_ids_pack_blocks(uint64_t n_ids, uint64_t n, int has_sep, uint32_t block, int flags);
+
 /* Always-sufficient output capacities (elements) for n rows of total_bytes input bytes.
  * ak_bpe_encode_cap holds for flags 2 / 3; with clean_hinglish=False (flags 0 / 1) NFKC can
  * expand a char (U+FDFA: 3 bytes -> 18 code points): AK_BPE_NFKC_EXPANSION * total_bytes + 2n + 16. */
