@@ -45,6 +45,16 @@ constexpr int T_MAXR = 16;    // rows per tile (upper bound of the runtime R)
 // 13 / 14 stop after staging / D1 / D2 / N / S / C / F
 #define AK_KNOCKOUT 0
 #endif
+#ifndef AK_TILE_WIDE
+// the sweeps of the BPE tile kernel that take 128 elements per step, two adjacent ones per lane, so
+// the per-step scalar work (loop control, ballots, carries, the scan's read-out) is paid half as
+// often per element; a bit set: TW_D1 pass D1 over the whole tile, TW_F pass F. 0 = the 64-wide
+// code everywhere (what the SentencePiece, row-tile, per-call and fallback-wave callers instantiate).
+// Default: D1 only. The wide pass F measured 0.7 % faster on top of it but costs the kernel one more
+// spilled VGPR (12 bytes of scratch per lane against 8), so it stays compiled out.
+#define AK_TILE_WIDE 1
+#endif
+constexpr int TW_D1 = 1, TW_F = 8;
 constexpr uint64_t TILE_UNIT = AK_TILE_UNIT;  // rows per unit of the work queue (tiles pack greedily inside one)
 static_assert(TILE_UNIT <= 64, "a unit's fallback rows are one 64-bit mask");
 constexpr int T_E = T_BCAP + 2 * T_MAXR + 64;
@@ -566,7 +576,8 @@ __device__ AK_D2_INLINE D2Exact d2_exact(MemT &M, const uint16_t *P, const uint3
 
 // Shared front end of the tile kernels (BPE, SentencePiece):
 //   stage: 16-byte coalesced loads of the tile's bytes into LDS;
-//   D1: per row, 64 bytes per step: the positions of the UTF-8 lead bytes -> P (in M.w);
+//   D1: per row, 64 bytes per step: the positions of the UTF-8 lead bytes -> P (in M.w); WIDE & TW_D1:
+//       the whole tile in one sweep, 128 bytes per step (the same P);
 //   D2: the whole tile's chars, 64 per step: decode, hot word, nfc_trig, normalize_text map -> V
 //       (M.v) with V_B / V_E sentinels around each row.
 // A row whose NFC quick check trips or that holds invalid UTF-8 is marked in M.fb (the caller sends
@@ -575,7 +586,7 @@ __device__ AK_D2_INLINE D2Exact d2_exact(MemT &M, const uint16_t *P, const uint3
 // raw (with NFCD; a wave-uniform value, so the fallback wave inlines one copy of the tile for both
 // its texts): the rows are HF NFKC text already (hf_epoch_gather): V holds the chars themselves (no
 // normalize_text map, no nukta expansion); a char past U+FFFB is invalid here.
-template <int BCAP, class Mem, bool NFCD = false>
+template <int BCAP, class Mem, bool NFCD = false, int WIDE = 0>
 __device__ __forceinline__ TileRows tile_front(const RowArgs &a, uint64_t r0, uint64_t rend, const uint32_t *H, Mem &M,
                                                bool raw = false) {
     const bool RAW = NFCD && raw;
@@ -609,7 +620,47 @@ __device__ __forceinline__ TileRows tile_front(const RowArgs &a, uint64_t r0, ui
     // in D2: the chars' lengths must tile the row).
     uint16_t *P = M.w;
     uint32_t np = 0;
-    for (int i = 0; i < k; ++i) {
+    // WIDE & TW_D1: the tile's rows are contiguous bytes, so ONE sweep lists them all, 128 bytes per
+    // step, lane l taking bytes 2l and 2l + 1 (one packed u16 read). Where the rows start comes from
+    // a bitmap, one bit per staged byte, that the rows' lanes set with one LDS OR each (in V, free
+    // until D2); a lane's entries are its row marks and leads in byte order, placed by one scan per
+    // step: the same P as the per-row loop writes. That loop still takes a tile with an empty row
+    // (two marks on one byte) or a row that opens with a continuation byte (its leads are not listed).
+    bool swept = false;
+    if constexpr ((WIDE & TW_D1) != 0) {
+        static_assert(BCAP + 16 + 128 <= 32 * 32 && sizeof(M.v) >= 32 * 4, "the row-start bitmap: 32 dwords of V");
+        const int s = lane < k ? (int)(myoff - a0) : 0;
+        const uint32_t fbyte = M.bytes[s];
+        swept = k > 0 && !w_ballot(lane < k && (nextoff == myoff || (fbyte & 0xC0u) == 0x80u));
+        if (swept) {
+            uint32_t *BM = (uint32_t *)M.v;
+            if (lane < 32) BM[lane] = 0u;
+            w_sync();
+            if (lane < k) w_lds_or32(&BM[s >> 5], 1u << (s & 31));
+            w_sync();
+            const int s0 = (int)(S0 - a0), end = (int)(S1 - a0);
+            const uint16_t *B2 = (const uint16_t *)M.bytes;
+            uint16_t *dummy = M.w + (sizeof(M.w) / 2 - 64) + lane;  // (past P's end, as in D2)
+            for (int base = s0 & ~1; base < end; base += 128) {
+                const int p0 = base + 2 * lane;
+                const int pc = p0 < (end & ~1) ? p0 : (end & ~1);
+                const uint32_t bb = B2[pc >> 1];
+                const uint32_t mk = (BM[p0 >> 5] >> (p0 & 31)) & 3u;  // (p0 is even: both bits in one dword)
+                const bool l0 = p0 >= s0 && p0 < end && (bb & 0xC0u) != 0x80u;
+                const bool l1 = p0 + 1 < end && (bb & 0xC000u) != 0x8000u;
+                const uint32_t m0 = mk & 1u, m1 = mk >> 1;
+                const uint32_t n0 = (uint32_t)l0 + m0;
+                uint32_t tot;
+                const uint32_t at = np + w_exscan(n0 + (uint32_t)l1 + m1, &tot);
+                *(m0 ? &P[at] : dummy) = 0x8000u;
+                *(l0 ? &P[at + m0] : dummy) = (uint16_t)p0;
+                *(m1 ? &P[at + n0] : dummy) = 0x8000u;
+                *(l1 ? &P[at + n0 + m1] : dummy) = (uint16_t)(p0 + 1);
+                np += tot;
+            }
+        }
+    }
+    for (int i = 0; i < (swept ? 0 : k); ++i) {
         const int s = (int)(w_bcast(myoff, i) - a0), e = (int)(w_bcast(myoff, i + 1) - a0);
         if (lane == 0) P[np] = 0x8000u;
         ++np;
@@ -1065,7 +1116,7 @@ __device__ __forceinline__ void pool_drain(const TileArgs &ta, TileWaveMem &M, u
     }
 }
 
-template <int FLAGS, bool NFCD = false>
+template <int FLAGS, bool NFCD = false, int WIDE = 0>
 __device__ __forceinline__ int bpe_tile(const TileArgs &ta, uint64_t r0, uint64_t rend, const uint32_t *H, const uint16_t *sfast,
                         TileWaveMem &M, uint4 *pool, PassClock &pc, bool raw = false) {
     const bool RAW = NFCD && raw;  // (the HF text: normalize_text and the HF check off)
@@ -1074,7 +1125,7 @@ __device__ __forceinline__ int bpe_tile(const TileArgs &ta, uint64_t r0, uint64_
     const RowArgs &a = ta.ra;
     const BpeDev &m = a.bpe;
     pc.mark(TP_STAGE);
-    const TileRows tr = tile_front<T_BCAP, TileWaveMem, NFCD>(a, r0, rend, H, M, raw);
+    const TileRows tr = tile_front<T_BCAP, TileWaveMem, NFCD, WIDE>(a, r0, rend, H, M, raw);
     const int nr = tr.nr;
     const uint32_t vlen = tr.vlen;
     if (AK_KNOCKOUT == 10) return nr;
@@ -1340,7 +1391,44 @@ __device__ __forceinline__ int bpe_tile(const TileArgs &ta, uint64_t r0, uint64_
     uint32_t pos = 0;
     uint32_t rs = 0;
     bool over = false;
-    for (uint32_t base = 0; base < wlen; base += 64) {
+    // WIDE & TW_F: 128 W entries per step, lane l taking entries 2l and 2l + 1 (one dword read, one
+    // dword of V written). With no fallback row in the tile (the usual case; else the 64-wide loop
+    // below runs) whether an entry is emitted does not depend on its row, so ONE scan over the packed
+    // pair (rows opened | entries emitted << 16) gives both ranks, and nothing is balloted.
+    const bool wide_f = (WIDE & TW_F) != 0 && FM == 0;
+    if (wide_f) {
+        static_assert(2 * T_SCAP + 64 * 4 <= (int)sizeof(TileWaveMem::bytes), "pass F's dummy slots past the miss list");
+        uint32_t *dummy = (uint32_t *)(M.bytes + 2 * T_SCAP) + lane;  // for the lanes that open no row / are past W
+        const uint32_t *W32 = (const uint32_t *)M.w;
+        uint32_t *V32 = (uint32_t *)M.v;
+        const uint32_t lim = scap < 0xFFFFFFFFull ? (uint32_t)scap : 0xFFFFFFFFu;  // (a tile emits < 2^12 entries)
+        for (uint32_t base = 0; base < wlen; base += 128) {
+            const uint32_t k0 = base + 2u * (uint32_t)lane;
+            const bool in0 = k0 < wlen, in1 = k0 + 1 < wlen;
+            const uint32_t ww = W32[(in0 ? k0 : 0u) >> 1];
+            const uint32_t x0 = in0 ? (ww & 0xFFFFu) : (uint32_t)V_DEAD, x1 = in1 ? (ww >> 16) : (uint32_t)V_DEAD;
+            const uint32_t b0 = (x0 == V_B) | (x0 == V_FB), b1 = (x1 == V_B) | (x1 == V_FB);
+            const uint32_t e0 = (x0 != V_FB) & (x0 != V_DEAD), e1 = (x1 != V_FB) & (x1 != V_DEAD);
+            uint32_t tot;
+            const uint32_t ex = w_exscan((b0 + b1) | ((e0 + e1) << 16), &tot);
+            const uint32_t rb = rs + (ex & 0xFFFFu);  // rows opened below this lane
+            const uint32_t op0 = pos + (ex >> 16), op1 = op0 + e0;
+            const uint32_t row0 = rb + b0 - 1u, row1 = row0 + b1;
+            *(b0 ? &M.rowop[rb] : dummy) = op0;  // read after the loop (counts)
+            *(b1 ? &M.rowop[rb + b0] : dummy) = op1;
+            const uint32_t t0 = e0 ? ((op0 | (row0 << 12)) & 0xFFFFu) : 0xFFFFu;
+            const uint32_t t1 = e1 ? ((op1 | (row1 << 12)) & 0xFFFFu) : 0xFFFFu;
+            *(in0 ? &V32[k0 >> 1] : dummy) = t0 | (t1 << 16);  // (one entry past W's end when wlen is odd: unread)
+            const uint32_t v0 = x0 == V_B ? m.bos : x0 == V_E ? m.eos : (x0 & 0x7FFFu);
+            const uint32_t v1 = x1 == V_B ? m.bos : x1 == V_E ? m.eos : (x1 & 0x7FFFu);
+            if (e0 && op0 < lim) stage[op0] = v0;
+            if (e1 && op1 < lim) stage[op1] = v1;
+            pos += tot >> 16;
+            rs += tot & 0xFFFFu;
+        }
+        over = pos > lim;  // the emitted places are 0 .. pos - 1: one of them is past the run's room
+    }
+    for (uint32_t base = 0; base < (wide_f ? 0u : wlen); base += 64) {
         const uint32_t kk = base + lane;
         const bool in = kk < wlen;
         const uint16_t x = in ? M.w[kk] : V_DEAD;
@@ -1455,7 +1543,7 @@ __device__ __forceinline__ void bpe_tiles_wave(const TileArgs &ta, const uint32_
         }
         w_sync();
         for (uint64_t r = r0; r < r1;)
-            r += (uint64_t)bpe_tile<FLAGS>(ta, r, r + (uint64_t)ta.rows < r1 ? r + (uint64_t)ta.rows : r1, H, sfast, M, pool, pc);
+            r += (uint64_t)bpe_tile<FLAGS, false, AK_TILE_WIDE>(ta, r, r + (uint64_t)ta.rows < r1 ? r + (uint64_t)ta.rows : r1, H, sfast, M, pool, pc);
         if (w_lane() == 0) {
             ta.unit_fb[t] = M.ufbm;
             ta.unit_len[t] = (uint32_t)(M.unext - run0);

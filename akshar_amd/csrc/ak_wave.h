@@ -84,6 +84,10 @@ inline uint32_t w_atomic_add32(uint32_t *p, uint32_t v) {
     return reinterpret_cast<std::atomic<uint32_t> *>(p)->fetch_add(v, std::memory_order_relaxed);
 }
 inline void w_sleep() {}
+// *p |= v on a word of the wave's LDS that several lanes may hit at once
+inline void w_lds_or32(uint32_t *p, uint32_t v) {
+    reinterpret_cast<std::atomic<uint32_t> *>(p)->fetch_or(v, std::memory_order_relaxed);
+}
 }  // namespace ak
 inline uint64_t clock64() { return 0; }
 inline unsigned long long atomicAdd(unsigned long long *p, unsigned long long v) {
@@ -171,6 +175,10 @@ __device__ __forceinline__ uint32_t w_atomic_add32(uint32_t *p, uint32_t v) {
     return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void w_sleep() { __builtin_amdgcn_s_sleep(2); }
+// *p |= v on a word of the wave's LDS that several lanes may hit at once (ds_or_b32, no return)
+__device__ __forceinline__ void w_lds_or32(uint32_t *p, uint32_t v) {
+    (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
 }  // namespace ak
 #endif
 
