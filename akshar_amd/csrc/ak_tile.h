@@ -48,13 +48,17 @@ constexpr int T_MAXR = 16;    // rows per tile (upper bound of the runtime R)
 #ifndef AK_TILE_WIDE
 // the sweeps of the BPE tile kernel that take 128 elements per step, two adjacent ones per lane, so
 // the per-step scalar work (loop control, ballots, carries, the scan's read-out) is paid half as
-// often per element; a bit set: TW_D1 pass D1 over the whole tile, TW_F pass F. 0 = the 64-wide
+// often per element; a bit set: TW_D1 (1) pass D1 over the whole tile, TW_N (4) pass N, TW_F (8)
+// pass F, TW_NS (16) pass S folded into the wide pass N (it brings TW_N with it). 0 = the 64-wide
 // code everywhere (what the SentencePiece, row-tile, per-call and fallback-wave callers instantiate).
-// Default: D1 only. The wide pass F measured 0.7 % faster on top of it but costs the kernel one more
-// spilled VGPR (12 bytes of scratch per lane against 8), so it stays compiled out.
-#define AK_TILE_WIDE 1
+// Default: every bit (29). The wide pass N alone is +3.9 % on cfg4. With the S fold and the wide pass F
+// on top the kernel stays at 64 VGPRs and 8 bytes of scratch per lane, the parent's figures, and gains
+// another 0.08 ms; without the fold the wide F spills (D1 + N + F: 28 bytes of scratch per lane, D1 + F:
+// 12), which is why the fold is on although by itself, on top of N, it measured 0.09 ms slower than
+// the separate pass S.
+#define AK_TILE_WIDE 29
 #endif
-constexpr int TW_D1 = 1, TW_F = 8;
+constexpr int TW_D1 = 1, TW_N = 4, TW_F = 8, TW_NS = 16;
 constexpr uint64_t TILE_UNIT = AK_TILE_UNIT;  // rows per unit of the work queue (tiles pack greedily inside one)
 static_assert(TILE_UNIT <= 64, "a unit's fallback rows are one 64-bit mask");
 constexpr int T_E = T_BCAP + 2 * T_MAXR + 64;
@@ -1140,6 +1144,121 @@ __device__ __forceinline__ int bpe_tile(const TileArgs &ta, uint64_t r0, uint64_
     //               (unk_token None); the first kept id of each pre-token carries WSTART
     // "previous" always means the previous KEPT element (shuffled from its lane or carried over).
     uint32_t wlen = 0;
+    uint32_t nw = 0;  // pre-tokens of >= 2 symbols listed (pass S, or pass N itself with TW_NS)
+    constexpr bool WNS = (WIDE & TW_NS) != 0, WN = (WIDE & TW_N) != 0 || WNS;  // (the fold lives in the wide pass N)
+    // WIDE & TW_NS: the list of pass S lives in the staged bytes (dead after D2), not at the top of V,
+    // which pass N is still reading while it lists; pass N's dummy slots move past the list. Pass C
+    // compacts its miss list over it in place (miss j is never written above list index j).
+    static_assert(2 * (T_SCAP + 64) <= (int)sizeof(TileWaveMem::bytes), "the start list + pass N's dummy slots in the staged bytes");
+    uint16_t *const slist = (uint16_t *)M.bytes;
+    // WIDE & TW_N: 128 V entries per step, lane l taking entries 2l and 2l + 1 (three dword reads: its
+    // pair and the pairs on either side, which hold prev, prev2 and next). The previous kept element
+    // of the odd entry is the even one if kept, else the last kept of the nearest lower lane that
+    // kept any (one ballot, one shuffle per step); the class travels inside the hot word. The word
+    // index, the place in W and the row counter come from ONE scan over packed per-lane counts
+    // (starts | emitted << 8 | rows << 16, each <= 128 per step), and the step's carries are what
+    // lane 63 holds. W, wlen and M.fb are what the 64-wide loop below writes.
+    // WIDE & TW_NS: an emitted id that continues a pre-token (no WSTART) right after that pre-token's
+    // first id is the second symbol of a pre-token of >= 2 symbols: its lane lists the place before
+    // its own, in order (a second scan), which is pass S's list. (Nothing is emitted between the two:
+    // a sentinel between two kept chars always opens a new pre-token.)
+    if constexpr (WN) {
+        uint16_t *dummy = (uint16_t *)M.bytes + (WNS ? T_SCAP : 0) + lane;
+        const uint32_t *V32 = (const uint32_t *)M.v;
+        const uint32_t h_sp = H[0x20];
+        uint32_t carry_h = H_ROWSTART, carry_word = 0, carry_kword = 0xFFFFFFFFu, carry_ks = 0, rs = 0;
+        const uint32_t dlast = (vlen ? vlen - 1 : 0) >> 1;
+        auto cls_of = [](uint32_t h) -> uint32_t { return h == H_ROWSTART ? (uint32_t)HF_S : ((h >> H_CLS_SHIFT) & 3u); };
+        for (uint32_t base = 0; base < vlen; base += 128) {
+            const uint32_t k0 = base + 2u * (uint32_t)lane;
+            const uint32_t d = k0 >> 1;
+            const uint32_t dc = d < dlast ? d : dlast;
+            const uint32_t wp = V32[dc >= 1 ? dc - 1 : 0], wx = V32[dc], wn = V32[dc < dlast ? dc + 1 : dlast];
+            const bool in0 = k0 < vlen, in1 = k0 + 1 < vlen;
+            const bool hasp = in0 && k0 >= 2;
+            const uint32_t x0 = in0 ? (wx & 0xFFFFu) : (uint32_t)V_DEAD, x1 = in1 ? (wx >> 16) : (uint32_t)V_DEAD;
+            const uint32_t pa0 = hasp ? (wp >> 16) : (uint32_t)V_DEAD, pb0 = hasp ? (wp & 0xFFFFu) : (uint32_t)V_DEAD;
+            const uint32_t nx1 = k0 + 2 < vlen ? (wn & 0xFFFFu) : (uint32_t)V_DEAD;
+            const bool sp0 = x0 >= V_SPECIAL, sp1 = x1 >= V_SPECIAL;
+            // (entry 1's prev is x0 and its prev2 is pa0; entry 0's next is x1)
+            const bool drop0 = !RAW && in0 && !sp0 && x0 != (uint32_t)'\n' && x0 == pa0 && (pa0 == pb0 || x1 == x0);
+            const bool drop1 = !RAW && in1 && !sp1 && x1 != (uint32_t)'\n' && x1 == x0 && (x0 == pa0 || nx1 == x1);
+            const bool keep0 = in0 && !drop0, keep1 = in1 && !drop1;
+            const uint32_t xi0 = x0 < HOT_LO ? x0 : (x0 - 0x900u < 0x100u ? x0 - 0x900u + HOT_LO : 0u);
+            const uint32_t xi1 = x1 < HOT_LO ? x1 : (x1 - 0x900u < 0x100u ? x1 - 0x900u + HOT_LO : 0u);
+            uint32_t h0 = H[xi0], h1 = H[xi1];
+            const bool cold0 = !sp0 && xi0 == 0u && x0 != 0u, cold1 = !sp1 && xi1 == 0u && x1 != 0u;
+            if (w_ballot(cold0 || cold1)) {
+                if (cold0) h0 = hot_of(prop_global(x0));
+                if (cold1) h1 = hot_of(prop_global(x1));
+            }
+            h0 = sp0 ? H_ROWSTART : h0;
+            h1 = sp1 ? H_ROWSTART : h1;
+            const bool hs0 = !sp0 && (h0 & H_HFSPACE), hs1 = !sp1 && (h1 & H_HFSPACE);
+            const uint32_t c0 = hs0 ? 0x20u : x0, c1 = hs1 ? 0x20u : x1;
+            h0 = hs0 ? h_sp : h0;
+            h1 = hs1 ? h_sp : h1;
+            const uint32_t cls0 = cls_of(h0), cls1 = cls_of(h1);
+            const uint64_t lt = w_lanemask_lt();
+            const uint64_t pk = w_ballot(keep0 || keep1) & lt;
+            const uint32_t h_l = w_shfl(keep1 ? h1 : h0, pk ? msb64(pk) : 0);
+            const uint32_t hprev0 = pk ? h_l : carry_h;
+            const uint32_t hprev1 = keep0 ? h0 : hprev0;
+            const bool hfc0 = keep0 && !sp0 && !(h0 & H_HFST), hfc1 = keep1 && !sp1 && !(h1 & H_HFST);
+            const bool trig0 = hfc0 && nfc_trig<true>(h0, hprev0), trig1 = hfc1 && nfc_trig<true>(h1, hprev1);
+            const bool hpc0 = hfc0 && nfc_pair_cand(h0, hprev0), hpc1 = hfc1 && nfc_pair_cand(h1, hprev1);
+            // pre-tokenizer + ids
+            const bool wc0 = keep0 && !sp0 && cls0 != (uint32_t)HF_S, wc1 = keep1 && !sp1 && cls1 != (uint32_t)HF_S;
+            const uint32_t st0 = wc0 && cls0 != cls_of(hprev0), st1 = wc1 && cls1 != cls_of(hprev1);
+            const uint32_t si0 = sfast_index(c0), si1 = sfast_index(c1);
+            uint32_t id0 = sfast[si0 < SFAST_N ? si0 : 0u], id1 = sfast[si1 < SFAST_N ? si1 : 0u];
+            const bool rare0 = wc0 && si0 >= SFAST_N, rare1 = wc1 && si1 >= SFAST_N;
+            if (w_ballot(rare0 || rare1)) {
+                if (rare0) id0 = single_id_of(m, sfast, a.single_fast, c0);
+                if (rare1) id1 = single_id_of(m, sfast, a.single_fast, c1);
+            }
+            id0 = wc0 ? id0 : 0xFFFFu;
+            id1 = wc1 ? id1 : 0xFFFFu;
+            const bool kept0 = id0 != 0xFFFFu, kept1 = id1 != 0xFFFFu;
+            const uint32_t out0 = kept0 || (keep0 && sp0), out1 = kept1 || (keep1 && sp1);
+            const uint32_t rm0 = keep0 && (x0 == V_B || x0 == V_FB), rm1 = keep1 && (x1 == V_B || x1 == V_FB);
+            uint32_t tot;
+            const uint32_t ex = w_exscan((st0 + st1) | ((out0 + out1) << 8) | ((rm0 + rm1) << 16), &tot);
+            // HF-NFC quick check -> row fallback (rare: behind a ballot), as in the 64-wide loop
+            if (!RAW && w_ballot(trig0 || hpc0 || trig1 || hpc1)) {
+                const uint32_t rrow0 = rs + (ex >> 16) + rm0 - 1u, rrow1 = rrow0 + rm1;
+                if (trig0 || (hpc0 && compose_pair<NF_HFK>(hprev0 & 0xFFFFu, c0))) M.fb[rrow0] |= 2;
+                if (trig1 || (hpc1 && compose_pair<NF_HFK>(hprev1 & 0xFFFFu, c1))) M.fb[rrow1] |= 2;
+            }
+            const uint32_t word0 = carry_word + (ex & 0xFFu) + st0, word1 = word0 + st1;  // inclusive
+            const uint64_t pk2 = w_ballot(kept0 || kept1) & lt;
+            const int src2 = pk2 ? msb64(pk2) : 0;
+            const uint32_t kw_l = w_shfl(kept1 ? word1 : word0, src2);
+            const uint32_t kprev0 = pk2 ? kw_l : carry_kword;
+            const uint32_t kprev1 = kept0 ? word0 : kprev0;
+            const bool ks0 = kept0 && word0 != kprev0, ks1 = kept1 && word1 != kprev1;
+            const uint32_t pos0 = wlen + ((ex >> 8) & 0xFFu), pos1 = pos0 + out0;
+            *(out0 ? &M.w[pos0] : dummy) = sp0 ? (uint16_t)x0 : (uint16_t)(id0 | (ks0 ? WSTART : 0u));
+            *(out1 ? &M.w[pos1] : dummy) = sp1 ? (uint16_t)x1 : (uint16_t)(id1 | (ks1 ? WSTART : 0u));
+            if constexpr (WNS) {
+                const uint32_t ks_l = w_shfl((uint32_t)(kept1 ? ks1 : ks0), src2);
+                const uint32_t pks0 = pk2 ? ks_l : carry_ks;
+                const uint32_t pks1 = kept0 ? (uint32_t)ks0 : pks0;
+                const uint32_t m0 = kept0 && !ks0 && pks0, m1 = kept1 && !ks1 && pks1;
+                uint32_t mtot;
+                const uint32_t j0 = nw + w_exscan(m0 + m1, &mtot), j1 = j0 + m0;
+                *(m0 && j0 < (uint32_t)T_SCAP ? &slist[j0] : dummy) = (uint16_t)(pos0 - 1u);
+                *(m1 && j1 < (uint32_t)T_SCAP ? &slist[j1] : dummy) = (uint16_t)(pos1 - 1u);
+                nw += mtot;
+                carry_ks = w_bcast((kept0 || kept1) ? (uint32_t)(kept1 ? ks1 : ks0) : pks0, 63);
+            }
+            wlen += (tot >> 8) & 0xFFu;
+            rs += tot >> 16;
+            carry_word += tot & 0xFFu;
+            carry_h = w_bcast((keep0 || keep1) ? (keep1 ? h1 : h0) : hprev0, 63);
+            carry_kword = w_bcast((kept0 || kept1) ? (kept1 ? word1 : word0) : kprev0, 63);
+        }
+    }
     {
         // Written branch-free where the lanes disagree: unconditional LDS loads at clamped indices,
         // table lookups with the rare code points (outside the LDS tables) behind a ballot, and
@@ -1150,7 +1269,7 @@ __device__ __forceinline__ int bpe_tile(const TileArgs &ta, uint64_t r0, uint64_
         uint32_t carry_h = H_ROWSTART, carry_word = 0, carry_kword = 0xFFFFFFFFu, rs = 0;
         int carry_cls = HF_S;
         const uint32_t vlast = vlen ? vlen - 1 : 0;
-        for (uint32_t base = 0; base < vlen; base += 64) {
+        for (uint32_t base = 0; base < (WN ? 0u : vlen); base += 64) {
             const uint32_t kk = base + lane;
             const bool in = kk < vlen;
             const uint32_t kc = in ? kk : vlast;
@@ -1252,8 +1371,8 @@ __device__ __forceinline__ int bpe_tile(const TileArgs &ta, uint64_t r0, uint64_
     // ---------------- pass S: starts of the pre-tokens with >= 2 symbols (a single symbol has
     // nothing to merge), to the TOP of V (V[T_E-1-k]) so pass B can use bytes + the bottom of V
     // for its rank rows (at most T_SCAP such pre-tokens; more: the tile's rows fall back).
-    uint32_t nw = 0;
-    for (uint32_t base = 0; base < wlen; base += 64) {
+    // (WIDE & TW_NS: pass N listed them, in the staged bytes)
+    for (uint32_t base = 0; base < (WNS ? 0u : wlen); base += 64) {
         const uint32_t kk = base + lane;
         const bool multi = kk + 1 < wlen && (M.w[kk] & 0x8000u) && M.w[kk] < V_SPECIAL && !(M.w[kk + 1] & 0x8000u);
         const uint64_t MM = w_ballot(multi);
@@ -1288,7 +1407,7 @@ __device__ __forceinline__ int bpe_tile(const TileArgs &ta, uint64_t r0, uint64_
         for (uint32_t wb = 0; wb < nw; wb += 64) {
             const uint32_t j = wb + lane;
             const bool act = j < nw;
-            const int st = act ? (int)M.v[T_E - 1 - j] : 0;
+            const int st = act ? (int)(WNS ? slist[j] : M.v[T_E - 1 - j]) : 0;
             uint32_t pr[WREG / 2];  // pr[k] = symbols 2k, 2k+1 of the window (low half first)
             {
                 uint32_t wd[WREG / 2 + 1];
