@@ -477,10 +477,14 @@ extern "C" int ak_spm_decode(const ak_spm *m, ak_ws *w, const uint32_t *ids, con
 extern "C" int ak_ws_create(ak_ws **out) {
     if (!out) return fail(AK_ERR_ARG, "ak_ws_create: null");
     ak_ws *w = new ak_ws();
-    HIP_TRY(hipMalloc(&w->ctr, 64));
-    HIP_TRY(hipMemset(w->ctr, 0, 64));
     const uint64_t bytes = pool_thread_bytes(SLOW_CAP) * SLOW_THREADS;
-    HIP_TRY(hipMalloc(&w->pool_mem, bytes));
+    hipError_t e = hipMalloc(&w->ctr, 64);
+    if (e == hipSuccess) e = hipMemset(w->ctr, 0, 64);
+    if (e == hipSuccess) e = hipMalloc(&w->pool_mem, bytes);
+    if (e != hipSuccess) {
+        ak_ws_free(w);
+        return ak::set_hip_error("ak_ws_create: hipMalloc", e);
+    }
     w->pool = pool_carve(w->pool_mem, SLOW_CAP, SLOW_THREADS);
     *out = w;
     return AK_OK;
@@ -500,7 +504,7 @@ extern "C" int ak_ws_check(ak_ws *w) {
     HIP_TRY(hipMemcpy(&err, w->ctr + CTR_ERR, 4, hipMemcpyDeviceToHost));
     if (err) return fail(AK_ERR_HIP, "internal: a row overflowed its staging slot or the huge tier (engine bug)");
     if (!w->tile_misc) return AK_OK;
-    HIP_TRY(hipMemcpy(&err, w->tile_misc + 1, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&err, w->tile_misc + TM_ERR, 4, hipMemcpyDeviceToHost));
     return err ? fail(AK_ERR_HIP, "tile staging slot overflow (a row produced more ids than bytes + 2)") : AK_OK;
 }
 
@@ -511,19 +515,16 @@ extern "C" int ak_ws_fallback_detail(ak_ws *w, uint64_t detail[4]) {
     if (!w || !detail) return fail(AK_ERR_ARG, "ak_ws_fallback_detail: null argument");
     for (int i = 0; i < 4; ++i) detail[i] = 0;
     if (!w->tile_misc) return AK_OK;
-    uint32_t h[8] = {};
+    uint32_t h[TM_N] = {};
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h, w->tile_misc, sizeof(h), hipMemcpyDeviceToHost));
-    // tile_misc: [0] fallback list, [2] slow tier, [4] SPM send-backs, [5] rows k_*_nfc passed on
-    // ([6]: 1 when the last launch was SPM; [7] the send-backs k_spm_redo passed on to the fallback
-    // list, which [0] and [4] both count)
-    const bool spm = h[6] != 0;
-    const uint64_t one_lane = std::min(h[0], h[5]);
-    const uint64_t dup = spm ? std::min(h[7], h[4]) : 0u;
-    detail[0] = spm ? (uint64_t)h[0] + h[4] - dup : h[0];
-    detail[1] = (spm ? h[4] : 0u) + h[0] - one_lane - dup;
+    const bool spm = h[TM_SPM] != 0;
+    const uint64_t one_lane = std::min(h[TM_FB], h[TM_PASSON]);
+    const uint64_t dup = spm ? std::min(h[TM_REDO_PASSON], h[TM_REDO]) : 0u;  // send-backs counted in both lists
+    detail[0] = spm ? (uint64_t)h[TM_FB] + h[TM_REDO] - dup : h[TM_FB];
+    detail[1] = (spm ? h[TM_REDO] : 0u) + h[TM_FB] - one_lane - dup;
     detail[2] = one_lane;
-    detail[3] = h[2];
+    detail[3] = h[TM_FB2];
     return AK_OK;
 }
 
@@ -532,11 +533,11 @@ extern "C" int ak_ws_fallback_rows(ak_ws *w, uint64_t *rows, uint64_t *pool_rows
     *rows = 0;
     *pool_rows = 0;
     if (!w->tile_misc) return AK_OK;
-    uint32_t h[3] = {0, 0, 0};
+    uint32_t h[TM_FB2 + 1] = {};
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(h, w->tile_misc, sizeof(h), hipMemcpyDeviceToHost));
-    *rows = h[0];
-    *pool_rows = h[2];
+    *rows = h[TM_FB];
+    *pool_rows = h[TM_FB2];
     return AK_OK;
 }
 
@@ -593,27 +594,9 @@ extern "C" void ak_ws_free(ak_ws *w) {
     delete w;
 }
 
-int ak::ws_reserve(AkWs *w, uint64_t n) {
-    if (n > w->cap_rows) {
-        uint64_t c = std::max<uint64_t>(n, 2 * w->cap_rows);
-        (void)hipFree(w->counts);
-        (void)hipFree(w->slow_list);
-        (void)hipFree(w->huge_list);
-        w->counts = nullptr; w->slow_list = nullptr; w->huge_list = nullptr;
-        HIP_TRY(hipMalloc(&w->counts, c * 4));
-        HIP_TRY(hipMalloc(&w->slow_list, c * 4));
-        HIP_TRY(hipMalloc(&w->huge_list, c * 4));
-        w->cap_rows = c;
-    }
-    const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE + 1;
-    if (nb > w->cap_blocks) {
-        uint64_t c = std::max<uint64_t>(nb, 2 * w->cap_blocks);
-        (void)hipFree(w->block_sums);
-        w->block_sums = nullptr;
-        HIP_TRY(hipMalloc(&w->block_sums, c * 8));
-        w->cap_blocks = c;
-    }
-    return AK_OK;
+int ak::ws_reserve(AkWs *w, uint64_t n, hipStream_t st) {
+    const int rc = ws_grow_rows(w, n, st);
+    return rc ? rc : ws_grow(w->block_sums, w->cap_blocks, (n + SCAN_TILE - 1) / SCAN_TILE + 1, st, GROW_X2);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -654,18 +637,12 @@ int ak::huge_prepare(AkWs *w, const uint64_t *offs, hipStream_t st, Tier *t, uns
     uint64_t threads = std::min<uint64_t>(h[0], SLOW_THREADS);
     while (threads > 1 && threads * per > HUGE_POOL_BUDGET) threads = (threads + 1) / 2;
     const uint64_t bytes = threads * per;
-    if (bytes > w->huge_bytes) {
-        (void)hipFree(w->huge_mem);
-        w->huge_mem = nullptr;
-        w->huge_bytes = 0;
-        if (hipMalloc(&w->huge_mem, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            char msg[160];
-            snprintf(msg, sizeof(msg), "huge tier: cannot allocate %llu bytes for a %u-byte row",
-                     (unsigned long long)bytes, h[1]);
-            return fail(AK_ERR_NOMEM, msg);
-        }
-        w->huge_bytes = bytes;
+    if (ws_grow(w->huge_mem, w->huge_bytes, bytes, st)) {
+        (void)hipGetLastError();
+        char msg[160];
+        snprintf(msg, sizeof(msg), "huge tier: cannot allocate %llu bytes for a %u-byte row",
+                 (unsigned long long)bytes, h[1]);
+        return fail(AK_ERR_NOMEM, msg);
     }
     t->list = w->huge_list;
     t->count = w->ctr + CTR_HUGE;
@@ -994,14 +971,8 @@ static int encode_host(ak_ws *w, const uint8_t *text, uint64_t len, int32_t *ids
         HIP_TRY(hipHostMalloc(&w->pin, c, hipHostMallocDefault));
         w->cap_pin = c;
     }
-    if (w->cap_dev1 < total) {
-        (void)hipFree(w->dev1);  // every earlier call synchronized before returning
-        w->dev1 = nullptr;
-        w->cap_dev1 = 0;
-        const uint64_t c = std::max<uint64_t>(total, 64 * 1024);
-        HIP_TRY(hipMalloc(&w->dev1, c));
-        w->cap_dev1 = c;
-    }
+    // (at least 64 KB, then what the longest row so far needed: cap_dev1 is 0 or >= 64 KB)
+    if (const int rc = ws_grow(w->dev1, w->cap_dev1, std::max<uint64_t>(total, 64 * 1024), st)) return rc;
     uint64_t *po = (uint64_t *)w->pin;
     po[0] = 0;
     po[1] = len;

@@ -14,6 +14,7 @@
 #include "akshar.h"
 #include "ak_dev.h"
 #include "ak_rows.h"
+#include "ak_ws_grow.h"
 
 namespace ak {
 
@@ -35,19 +36,34 @@ constexpr uint64_t SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;
 // CTR_ERR: an internal overflow (ak_ws_check: engine bug); CTR_DEC_ARG: an SPM decode id past the
 // vocabulary (the caller's argument error, reported by ak_spm_decode itself)
 enum { CTR_SLOW = 0, CTR_HUGE = 1, CTR_ERR = 2, CTR_DEC_ARG = 3, CTR_N = 4 };
+// AkWs::tile_misc, the per-launch words of a tile launch (TM_WORDS allocated; every launcher clears
+// the first TM_N but launch_bpe_tiles, which leaves SentencePiece's TM_REDO_PASSON alone):
+//   TM_FB           length of the fallback list (rows the tile kernel sent to the fallback kernels)
+//   TM_ERR          slot-overflow flag (ak_ws_check reports the last launch's)
+//   TM_FB2          length of the second list (rows past the one-lane kernel's buffers: the slow tier)
+//   TM_QUEUE        the work queue: next unit to take
+//   TM_REDO         SentencePiece: rows the word pool sent back (k_spm_redo)
+//   TM_PASSON       rows the fallback waves (k_*_nfc) passed on to the one-lane kernel (fb3's length)
+//   TM_SPM          1 when the last launch was SentencePiece (ak_ws_fallback_detail)
+//   TM_REDO_PASSON  SentencePiece: send-backs k_spm_redo passed on to the fallback list (in TM_FB and TM_REDO)
+enum { TM_FB = 0, TM_ERR = 1, TM_FB2 = 2, TM_QUEUE = 3, TM_REDO = 4, TM_PASSON = 5, TM_SPM = 6, TM_REDO_PASSON = 7,
+       TM_N = 8, TM_WORDS = 64 };
 constexpr uint64_t HUGE_POOL_BUDGET = 4ull << 30;  // bytes the huge tier may use for parallel rows
 
 struct AkWs {
-    uint64_t cap_rows = 0;
-    uint32_t *counts = nullptr;
-    uint32_t *slow_list = nullptr;  // rows for the slow tier (n entries)
-    uint32_t *huge_list = nullptr;  // rows for the huge tier (n entries)
+    // every "buffer + cap_*" pair below grows through ws_grow (ak_ws_grow.h) and nowhere else
+    uint32_t *counts = nullptr;     // per-row counts (ws_reserve: n entries, as the two lists)
+    uint64_t cap_counts = 0;
+    uint32_t *slow_list = nullptr;  // rows for the slow tier; the tile launchers' fallback list
+    uint64_t cap_slow = 0;
+    uint32_t *huge_list = nullptr;  // rows for the huge tier
+    uint64_t cap_huge = 0;
     uint32_t *ctr = nullptr;        // CTR_N launch counters + scratch for huge_prepare
     uint64_t *block_sums = nullptr;
     uint64_t cap_blocks = 0;
     void *pool_mem = nullptr;
     SlowPool pool{};
-    void *huge_mem = nullptr;       // huge-tier pool, grown on demand
+    uint8_t *huge_mem = nullptr;    // huge-tier pool, grown on demand
     uint64_t huge_bytes = 0;
     // tile-cooperative BPE path
     uint32_t *stage = nullptr;      // staged ids, slot of row r at offs[r] + 2 r (tile BPE: unit runs +
@@ -57,7 +73,7 @@ struct AkWs {
     uint64_t cap_stage8 = 0;
     uint32_t *acounts = nullptr;    // analyze: cluster and run counts per row (2 n)
     uint64_t cap_acounts = 0;
-    uint32_t *tile_misc = nullptr;  // [0] fallback-list length, [1] slot-overflow flag, [2] second list length
+    uint32_t *tile_misc = nullptr;  // the tile launches' per-launch words (TM_*)
     uint32_t *fb2 = nullptr;        // second fallback list (rows past the fast buffers)
     uint64_t cap_fb2 = 0;
     uint64_t *unit_fb = nullptr;    // tile BPE: per 64-row unit, the mask of its fallback rows
@@ -130,9 +146,11 @@ void prof_mark(int kernel, bool end, hipStream_t st);
 #define AK_PROF(k, end, st) \
     do { if (ak::g_prof_on) ak::prof_mark((k), (end), (st)); } while (0)
 
-int ws_reserve(AkWs *w, uint64_t n);
-int ws_stage_reserve(AkWs *w, uint64_t need, hipStream_t st);
-int ws_stage8_reserve(AkWs *w, uint64_t need, hipStream_t st);
+int ws_reserve(AkWs *w, uint64_t n, hipStream_t st);
+inline int ws_stage_reserve(AkWs *w, uint64_t need, hipStream_t st) { return ws_grow(w->stage, w->cap_stage, need, st, GROW_X1_5); }
+inline int ws_stage8_reserve(AkWs *w, uint64_t need, hipStream_t st) { return ws_grow(w->stage8, w->cap_stage8, need, st, GROW_X1_5); }
+// analyze / the row tiles: cluster and run counts per row
+inline int ws_acounts_reserve(AkWs *w, uint64_t n, hipStream_t st) { return ws_grow(w->acounts, w->cap_acounts, 2 * n, st); }
 int launch_stage_copy(AkWs *w, const uint64_t *offs, const uint64_t *out_offs, uint64_t n, uint32_t *ids, uint64_t cap,
                       uint32_t mul, uint32_t add, hipStream_t st, uint8_t *labels = nullptr);
 int scan_counts(AkWs *w, uint64_t n, uint64_t *out_offs, hipStream_t st, const uint32_t *counts = nullptr);
@@ -141,12 +159,11 @@ int copy_staged(const T *stage, uint64_t stage_cap, const uint64_t *offs, const 
                 uint64_t cap, uint32_t mul, uint32_t add, hipStream_t st);
 int num_cus();
 
-// Grid of a fallback-row kernel: as many blocks as stay resident on every CU (its rows run one lane
-// each, sequential and latency-bound, so resident lanes are the lever). The occupancy is cached
-// per launcher in an atomic: host threads driving different GPUs may race on it, and every device
-// of the node is the same gfx950 part, so one value serves them all (a benign, idempotent store).
+// Blocks of a kernel that stay resident on one CU. The occupancy is cached per kernel in an atomic:
+// host threads driving different GPUs may race on it, and every device of the node is the same
+// gfx950 part, so one value serves them all (a benign, idempotent store).
 template <class K>
-unsigned resident_grid(K kernel, int block, std::atomic<int> &cache) {
+int blocks_per_cu(K kernel, int block, std::atomic<int> &cache) {
     int c = cache.load(std::memory_order_relaxed);
     if (!c) {
         int b = 0;
@@ -154,10 +171,15 @@ unsigned resident_grid(K kernel, int block, std::atomic<int> &cache) {
         c = b > 1 ? b : 1;
         cache.store(c, std::memory_order_relaxed);
     }
-    return (unsigned)num_cus() * (unsigned)c;
+    return c;
 }
-// unit-run staging (tile BPE, row tiles): per-unit fallback masks, and the streaming unit copy
-int ws_unit_fb_reserve(AkWs *w, uint64_t nunits);
+// Grid of a fallback-row kernel: as many blocks as stay resident on every CU (its rows run one lane
+// each, sequential and latency-bound, so resident lanes are the lever).
+template <class K>
+unsigned resident_grid(K kernel, int block, std::atomic<int> &cache) {
+    return (unsigned)num_cus() * (unsigned)blocks_per_cu(kernel, block, cache);
+}
+// unit-run staging (tile BPE, row tiles): the streaming unit copy
 template <class T>
 int copy_units(const T *stage, const T *stage_fb, uint64_t half, const uint64_t *offs, const uint64_t *out_offs,
                const uint64_t *unit_fb, uint64_t n, T *out, uint64_t cap, uint32_t mul, uint32_t add, hipStream_t st);
@@ -298,7 +320,7 @@ inline int launch_rows_staged(AkWs *w, RowArgs a, uint64_t *out_offs, hipStream_
         HIP_TRY(hipMemsetAsync(out_offs, 0, 8, st));
         return AK_OK;
     }
-    int rc = ws_reserve(w, a.n);
+    int rc = ws_reserve(w, a.n, st);
     if (rc) return rc;
     uint64_t nbytes = 0;  // one 8-byte read-back sizes the staging area
     if ((rc = ws_total_bytes(w, a.offs, a.n, st, &nbytes))) return rc;

@@ -104,14 +104,7 @@ static int launch(AkWs *w, RowArgs a, const AnalyzeOut &o, hipStream_t st) {
     if (rc) return rc;
     rc = ws_stage8_reserve(w, 2 * need, st);
     if (rc) return rc;
-    if (w->cap_acounts < 2 * a.n) {
-        HIP_TRY(hipStreamSynchronize(st));
-        (void)hipFree(w->acounts);
-        w->acounts = nullptr;
-        w->cap_acounts = 0;
-        HIP_TRY(hipMalloc(&w->acounts, 2 * a.n * 4));
-        w->cap_acounts = 2 * a.n;
-    }
+    if ((rc = ws_acounts_reserve(w, a.n, st))) return rc;
     AnalyzeArgs x;
     x.clus = w->stage;
     x.runs = w->stage + need;
@@ -159,7 +152,7 @@ int launch_analyze(int flags, AkWs *w, const RowArgs &a, const AnalyzeOut &o, hi
         HIP_TRY(hipMemsetAsync(o.run_offs, 0, 8, st));
         return AK_OK;
     }
-    int rc = ws_reserve(w, a.n);
+    int rc = ws_reserve(w, a.n, st);
     if (rc) return rc;
     switch (flags) {
         case 0: return launch<0>(w, a, o, st);

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "ak_internal.h"
+#include "ak_launch.h"
 #include "ak_nfc_wave.h"
 #include "ak_small.h"
 #include "ak_tile.h"
@@ -345,16 +346,6 @@ template int copy_units<uint8_t>(const uint8_t *, const uint8_t *, uint64_t, con
 template int copy_units<uint32_t>(const uint32_t *, const uint32_t *, uint64_t, const uint64_t *, const uint64_t *,
                                   const uint64_t *, uint64_t, uint32_t *, uint64_t, uint32_t, uint32_t, hipStream_t);
 
-int ws_unit_fb_reserve(AkWs *w, uint64_t nunits) {
-    if (w->cap_unit_fb >= nunits) return AK_OK;
-    (void)hipFree(w->unit_fb);
-    w->unit_fb = nullptr;
-    w->cap_unit_fb = 0;
-    HIP_TRY(hipMalloc(&w->unit_fb, nunits * 8));
-    w->cap_unit_fb = nunits;
-    return AK_OK;
-}
-
 // wave-primitive self-test (ak_selftest): DPP scan, readlane broadcast, ballot, DPP wave_shr on known patterns
 __global__ __launch_bounds__(64) void k_selftest(uint32_t *out) {
     const int lane = w_lane();
@@ -396,8 +387,6 @@ int selftest_wave() {
     return AK_OK;
 }
 
-static std::atomic<int> g_tile_blocks_per_cu{0};  // occupancy (same gfx950 part on every device; idempotent store)
-
 // flags == AK_NORM_DEFAULT only (the dispatcher sends other flags to the row kernels)
 int launch_bpe_tiles(int flags, AkWs *w, const RowArgs &a0, uint64_t *out_offs, hipStream_t st) {
     if (flags != 3) return set_error(AK_ERR_UNSUPPORTED, "bpe tiles: flags must be 3");
@@ -405,91 +394,30 @@ int launch_bpe_tiles(int flags, AkWs *w, const RowArgs &a0, uint64_t *out_offs, 
         HIP_TRY(hipMemsetAsync(out_offs, 0, 8, st));
         return AK_OK;
     }
-    int rc = ws_reserve(w, a0.n);
+    int rc = ws_reserve(w, a0.n, st);
     if (rc) return rc;
     // staging slot of row r starts at offs[r] + 2 r: size offs[n] + 2 n (one 8-byte read-back)
     uint64_t nbytes = 0;
     if ((rc = ws_total_bytes(w, a0.offs, a0.n, st, &nbytes))) return rc;
     // two halves: the tile kernel's unit runs, then the fallback rows' slots
     const uint64_t half = nbytes + 2 * a0.n + 64;
-    rc = ws_stage_reserve(w, 2 * half, st);
-    if (rc) return rc;
-    const int R = w->tile_rows;
-    const uint64_t ntiles = (a0.n + TILE_UNIT - 1) / TILE_UNIT;  // units of the work queue (ak_tile.h tile_first_unit)
-    if ((rc = ws_unit_fb_reserve(w, ntiles))) return rc;
-    if (w->cap_unit_len < ntiles) {
-        (void)hipFree(w->unit_len);
-        w->unit_len = nullptr;
-        w->cap_unit_len = 0;
-        HIP_TRY(hipMalloc(&w->unit_len, ntiles * 4));
-        w->cap_unit_len = ntiles;
-    }
-    if (!w->tile_misc) {  // [0] fb count, [1] overflow flag, [2] fb2 count, [3] the unit queue
-        HIP_TRY(hipMalloc(&w->tile_misc, 64 * 4));
-        HIP_TRY(hipMemsetAsync(w->tile_misc, 0, 64 * 4, st));
-    }
-    if (g_prof_passes && !w->tile_passprof) {
-        HIP_TRY(hipMalloc(&w->tile_passprof, T_NPROF * 8));
-        HIP_TRY(hipMemsetAsync(w->tile_passprof, 0, T_NPROF * 8, st));
-    }
-    if (!g_tile_blocks_per_cu.load(std::memory_order_relaxed)) {
-        int b = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_bpe_tiles<3>, TILE_BLOCK, 0));
-        g_tile_blocks_per_cu.store(std::max(1, b), std::memory_order_relaxed);
-    }
-    TileArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    ta.ra = a0;
+    if ((rc = ws_stage_reserve(w, 2 * half, st))) return rc;
+    if ((rc = tile_ws_prepare(w, a0.n, st))) return rc;
+    const uint64_t ntiles = (a0.n + TILE_UNIT - 1) / TILE_UNIT;
+    static std::atomic<int> tile_bpc{0};
+    const unsigned grid = tile_grid(k_bpe_tiles<3>, TILE_BLOCK, tile_bpc, ntiles, "AK_TILE_BPC");
+    // the merge pools: k_bpe_nfc's waves flush into their own wave slots, as the tile kernel's
+    if ((rc = tile_pool_reserve(w, st, (uint64_t)grid * (TILE_BLOCK / 64), fallback_waves(NFC_BLOCK), POOL_U4))) return rc;
+    TileArgs ta = tile_args_common(w, a0, ntiles);
     ta.ra.out = w->stage;
     ta.ra.cap = half;
-    ta.unit_fb = w->unit_fb;
-    ta.ra.out_offs = nullptr;
     ta.counts = w->counts;
-    ta.fb_list = w->slow_list;              // n entries (ws_reserve)
-    ta.fb_count = w->tile_misc;
-    ta.err = w->tile_misc + 1;
-    ta.fb2_count = w->tile_misc + 2;
-    ta.next_unit = w->tile_misc + 3;
-    ta.passprof = g_prof_passes ? w->tile_passprof : nullptr;
-    ta.ntiles = ntiles;
-    ta.rows = R;
-    if (w->cap_fb2 < a0.n) {
-        (void)hipFree(w->fb2);
-        w->fb2 = nullptr;
-        HIP_TRY(hipMalloc(&w->fb2, a0.n * 4));
-        w->cap_fb2 = a0.n;
-    }
-    ta.fb2_list = w->fb2;
-    if (w->cap_fb3 < a0.n) {
-        (void)hipFree(w->fb3);
-        w->fb3 = nullptr;
-        HIP_TRY(hipMalloc(&w->fb3, a0.n * 4));
-        w->cap_fb3 = a0.n;
-    }
-    // fallback count, overflow flag (ak_ws_check reports this call's), second fallback count
-    // [0..3] as above, [4] (SentencePiece's), [5] k_bpe_nfc's pass-on count, [6] 0: a BPE launch
-    static_assert(CTR_N <= 256, "k_tile_init's first block clears the counters");
-    k_tile_init<><<<1, 256, 0, st>>>(w->tile_misc, 7, 0u, w->ctr, CTR_N, nullptr, 0);
-    HIP_TRY(hipGetLastError());
-    const uint64_t waves_per_block = TILE_BLOCK / 64;
-    // AK_TILE_BPC (development aid): resident blocks per CU below the occupancy limit
-    int bpc = g_tile_blocks_per_cu.load(std::memory_order_relaxed);
-    if (const char *e = getenv("AK_TILE_BPC")) bpc = std::max(1, std::min(bpc, atoi(e)));
-    const unsigned grid = (unsigned)std::min<uint64_t>((ntiles + waves_per_block - 1) / waves_per_block,
-                                                       (uint64_t)num_cus() * (uint64_t)bpc);
-    // the waves' merge pools: POOL_CAP entries per wave slot of the grid, and of k_bpe_nfc's grid
-    // (num_cus() blocks of NFC_BLOCK / 64 waves, which a small launch's tile grid may not reach)
-    const uint64_t pool_waves = std::max<uint64_t>((uint64_t)grid * waves_per_block, (uint64_t)num_cus() * (NFC_BLOCK / 64));
-    const uint64_t pool_entries = pool_waves * POOL_U4;
-    if (w->cap_bpool < pool_entries) {
-        (void)hipFree(w->bpool);
-        w->bpool = nullptr;
-        w->cap_bpool = 0;
-        HIP_TRY(hipMalloc(&w->bpool, pool_entries * sizeof(uint4)));
-        w->cap_bpool = pool_entries;
-    }
+    ta.rows = w->tile_rows;
     ta.pool = w->bpool;
     ta.unit_len = w->unit_len;
+    // the per-launch words but SentencePiece's last, TM_SPM = 0, and the counters in one launch
+    k_tile_init<><<<1, 256, 0, st>>>(w->tile_misc, TM_REDO_PASSON, 0u, w->ctr, CTR_N, nullptr, 0);
+    HIP_TRY(hipGetLastError());
     AK_PROF(AK_PROF_TILES, false, st);
     k_bpe_tiles<3><<<grid, TILE_BLOCK, 0, st>>>(ta);
     AK_PROF(AK_PROF_TILES, true, st);
@@ -499,33 +427,13 @@ int launch_bpe_tiles(int flags, AkWs *w, const RowArgs &a0, uint64_t *out_offs, 
     AK_PROF(AK_PROF_FALLBACK_WAVE, false, st);
     TileArgs tfb = ta;
     tfb.ra.out = w->stage + half;
-    tfb.ra.cap = half;
-    if (!getenv("AK_NO_NFC_WAVE")) {  // (development aid: the one-lane path for every fallback row)
-        const unsigned ngrid = (unsigned)num_cus();
-        const uint64_t nw = (uint64_t)ngrid * (NFC_BLOCK / 64);
-        if (w->cap_nfc < nw) {
-            (void)hipFree(w->nfc_buf);
-            w->nfc_buf = nullptr;
-            w->cap_nfc = 0;
-            HIP_TRY(hipMalloc(&w->nfc_buf, nw * NE_BYTES));
-            w->cap_nfc = nw;
-        }
-        if (!w->comp_hash) {  // built once per workspace
-            HIP_TRY(hipMalloc(&w->comp_hash, CH_SLOTS * sizeof(uint4)));
-            HIP_TRY(hipMemsetAsync(w->comp_hash, 0, CH_SLOTS * sizeof(uint4), st));
-            k_comp_hash_build<><<<(AK_UT_NCOMP + 255) / 256, 256, 0, st>>>(w->comp_hash);
-            HIP_TRY(hipGetLastError());
-        }
-        tfb.comp_hash = w->comp_hash;
-        if (w->cap_bpool < nw * POOL_U4) return set_error(AK_ERR_HIP, "internal: merge pools smaller than k_bpe_nfc's grid");
-        // (no more waves than rows: a small call dispatches a block or two of the 156 KB kernel)
-        const unsigned lgrid = (unsigned)std::min<uint64_t>(ngrid, (a0.n + NFC_BLOCK / 64 - 1) / (NFC_BLOCK / 64));
-        k_bpe_nfc<3><<<lgrid, NFC_BLOCK, 0, st>>>(tfb, w->nfc_buf, w->fb3, w->tile_misc + 5);
+    unsigned lgrid = 0;
+    if ((rc = fallback_wave_prepare(w, st, a0.n, NFC_BLOCK, NE_BYTES, w->nfc_buf, w->cap_nfc, k_comp_hash_build<>, tfb, &lgrid)))
+        return rc;
+    if (lgrid) {
+        k_bpe_nfc<3><<<lgrid, NFC_BLOCK, 0, st>>>(tfb, w->nfc_buf, w->fb3, w->tile_misc + TM_PASSON);
         HIP_TRY(hipGetLastError());
-        tfb.fb_list = w->fb3;
-        tfb.fb_count = w->tile_misc + 5;
-    } else {  // every fallback row goes on (ak_ws_fallback_detail)
-        HIP_TRY(hipMemcpyAsync(w->tile_misc + 5, w->tile_misc, 4, hipMemcpyDeviceToDevice, st));
+        fallback_wave_passed(w, tfb);
     }
     AK_PROF(AK_PROF_FALLBACK_WAVE, true, st);
     AK_PROF(AK_PROF_EMIT_SLOW, false, st);
@@ -542,18 +450,15 @@ int launch_bpe_tiles(int flags, AkWs *w, const RowArgs &a0, uint64_t *out_offs, 
     if (rc) return rc;
     AK_PROF(AK_PROF_EMIT_SLOW, true, st);
     AK_PROF(AK_PROF_SCAN, false, st);
-    rc = scan_counts(w, a0.n, out_offs, st);
-    if (rc) return rc;
+    if ((rc = scan_counts(w, a0.n, out_offs, st))) return rc;
     AK_PROF(AK_PROF_SCAN, true, st);
     AK_PROF(AK_PROF_COPY, false, st);
-    {
-        const unsigned cgrid = (unsigned)std::min<uint64_t>((ntiles + 3) / 4, (uint64_t)num_cus() * 8);
-        k_unit_copy_bpe<<<cgrid, 256, 0, st>>>(w->stage, w->stage + half, a0.offs, out_offs, w->unit_fb, w->unit_len,
-                                               a0.n, (uint32_t *)a0.out, a0.cap, half);
-        HIP_TRY(hipGetLastError());
-    }
+    const unsigned cgrid = (unsigned)std::min<uint64_t>((ntiles + 3) / 4, (uint64_t)num_cus() * 8);
+    k_unit_copy_bpe<<<cgrid, 256, 0, st>>>(w->stage, w->stage + half, a0.offs, out_offs, w->unit_fb, w->unit_len, a0.n,
+                                           (uint32_t *)a0.out, a0.cap, half);
+    HIP_TRY(hipGetLastError());
     AK_PROF(AK_PROF_COPY, true, st);
-    return rc;
+    return AK_OK;
 }
 
 // One row (ta.ra.n == 1, at most T_BCAP bytes) through bpe_tile and the merge pool by ONE wave.
@@ -642,30 +547,6 @@ int small_call_wait(AkWs *w, hipStream_t st, uint32_t seq, uint32_t *status) {
     const uint32_t x = res[0];
     if ((x >> 2) != (seq & 0x3FFFFFFFu)) return set_error(AK_ERR_HIP, "internal: the per-call kernel wrote no status");
     *status = x & 3u;
-    return AK_OK;
-}
-
-int ws_stage_reserve(AkWs *w, uint64_t need, hipStream_t st) {
-    if (need <= w->cap_stage) return AK_OK;
-    HIP_TRY(hipStreamSynchronize(st));  // the old buffer may still be read by queued work
-    const uint64_t c = std::max<uint64_t>(need, w->cap_stage + w->cap_stage / 2);
-    (void)hipFree(w->stage);
-    w->stage = nullptr;
-    w->cap_stage = 0;
-    HIP_TRY(hipMalloc(&w->stage, c * 4));
-    w->cap_stage = c;
-    return AK_OK;
-}
-
-int ws_stage8_reserve(AkWs *w, uint64_t need, hipStream_t st) {
-    if (need <= w->cap_stage8) return AK_OK;
-    HIP_TRY(hipStreamSynchronize(st));
-    const uint64_t c = std::max<uint64_t>(need, w->cap_stage8 + w->cap_stage8 / 2);
-    (void)hipFree(w->stage8);
-    w->stage8 = nullptr;
-    w->cap_stage8 = 0;
-    HIP_TRY(hipMalloc(&w->stage8, c));
-    w->cap_stage8 = c;
     return AK_OK;
 }
 

@@ -138,7 +138,7 @@ int launch_decode(bool spm, AkWs *w, const DecTab &t, const uint32_t *ids, const
         HIP_TRY(hipMemsetAsync(out_offs, 0, 8, st));
         return AK_OK;
     }
-    int rc = ws_reserve(w, n);
+    int rc = ws_reserve(w, n, st);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(w->ctr, 0, CTR_N * 4, st));
     uint32_t *err = w->ctr + CTR_DEC_ARG;  // not CTR_ERR: a bad id is an argument error, not an engine bug

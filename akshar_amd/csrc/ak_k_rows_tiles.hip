@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "ak_internal.h"
+#include "ak_launch.h"
 #include "ak_tile_rows.h"
 
 namespace ak {
@@ -111,92 +112,33 @@ __global__ __launch_bounds__(64) void k_rows_tile_tier(RowArgs a, RowsOut o, Tie
     }
 }
 
-static int g_rt_bpc[8] = {};
-
 template <int OPS>
 static int launch_ops(AkWs *w, const RowArgs &a0, const RowsOut &o0, const RowsOut &ofb, const RowsOutFinal &f,
                       hipStream_t st) {
-    int rc;
-    if (!w->tile_misc) {  // [0] fb count, [1] overflow flag, [2] fb2 count, [3] the unit queue
-        HIP_TRY(hipMalloc(&w->tile_misc, 64 * 4));
-        HIP_TRY(hipMemsetAsync(w->tile_misc, 0, 64 * 4, st));
-    }
-    if (g_prof_passes && !w->tile_passprof) {
-        HIP_TRY(hipMalloc(&w->tile_passprof, T_NPROF * 8));
-        HIP_TRY(hipMemsetAsync(w->tile_passprof, 0, T_NPROF * 8, st));
-    }
-    if (!g_rt_bpc[OPS]) {
-        int b = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_rows_tiles<OPS>, RT_BLOCK, 0));
-        g_rt_bpc[OPS] = std::max(1, b);
-    }
-    if (w->cap_fb2 < a0.n) {
-        (void)hipFree(w->fb2);
-        w->fb2 = nullptr;
-        HIP_TRY(hipMalloc(&w->fb2, a0.n * 4));
-        w->cap_fb2 = a0.n;
-    }
+    int rc = tile_ws_prepare(w, a0.n, st);
+    if (rc) return rc;
     const uint64_t ntiles = (a0.n + TILE_UNIT - 1) / TILE_UNIT;
-    if ((rc = ws_unit_fb_reserve(w, ntiles))) return rc;
-    TileArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    ta.ra = a0;
-    ta.ra.out_offs = nullptr;
-    ta.counts = nullptr;
-    ta.fb_list = w->slow_list;
-    ta.fb_count = w->tile_misc;
-    ta.err = w->tile_misc + 1;
-    ta.fb2_list = w->fb2;
-    ta.fb2_count = w->tile_misc + 2;
-    ta.next_unit = w->tile_misc + 3;
-    ta.passprof = g_prof_passes ? w->tile_passprof : nullptr;
-    ta.ntiles = ntiles;
-    ta.unit_fb = w->unit_fb;
+    static std::atomic<int> tile_bpc{0};  // (one per OPS)
+    const unsigned grid = tile_grid(k_rows_tiles<OPS>, RT_BLOCK, tile_bpc, ntiles);
+    TileArgs ta = tile_args_common(w, a0, ntiles);
     ta.rows = std::min(w->tile_rows, T_MAXR);
-    // fallback count, overflow flag (ak_ws_check reports this call's), second fallback count, the
-    // unit queue, [5] the rows k_rows_nfc passes on; [6] = 0: not a SentencePiece launch
-    HIP_TRY(hipMemsetAsync(w->tile_misc, 0, 8 * 4, st));
+    // the per-launch words (TM_SPM = 0: not a SentencePiece launch) and the counters
+    HIP_TRY(hipMemsetAsync(w->tile_misc, 0, TM_N * 4, st));
     HIP_TRY(hipMemsetAsync(w->ctr, 0, CTR_N * 4, st));
-    const uint64_t wpb = RT_BLOCK / 64;
-    const unsigned grid = (unsigned)std::min<uint64_t>((ntiles + wpb - 1) / wpb, (uint64_t)num_cus() * g_rt_bpc[OPS]);
     AK_PROF(AK_PROF_ROW_TILES, false, st);
     k_rows_tiles<OPS><<<grid, RT_BLOCK, 0, st>>>(ta, o0);
     AK_PROF(AK_PROF_ROW_TILES, true, st);
     HIP_TRY(hipGetLastError());
     TileArgs tfb = ta;
-    if (!getenv("AK_NO_NFC_WAVE")) {  // (development aid: the one-lane path for every fallback row)
+    unsigned lgrid = 0;
+    if ((rc = fallback_wave_prepare(w, st, a0.n, RT_NFC_BLOCK, RE_BYTES, w->rnfc_buf, w->cap_rnfc, k_comp_hash_build<>, tfb, &lgrid)))
+        return rc;
+    if (lgrid) {
         AK_PROF(AK_PROF_FALLBACK_WAVE, false, st);
-        const unsigned ngrid = (unsigned)num_cus();
-        const uint64_t nw = (uint64_t)ngrid * (RT_NFC_BLOCK / 64);
-        if (w->cap_rnfc < nw) {
-            (void)hipFree(w->rnfc_buf);
-            w->rnfc_buf = nullptr;
-            w->cap_rnfc = 0;
-            HIP_TRY(hipMalloc(&w->rnfc_buf, nw * RE_BYTES));
-            w->cap_rnfc = nw;
-        }
-        if (w->cap_fb3 < a0.n) {
-            (void)hipFree(w->fb3);
-            w->fb3 = nullptr;
-            HIP_TRY(hipMalloc(&w->fb3, a0.n * 4));
-            w->cap_fb3 = a0.n;
-        }
-        if (!w->comp_hash) {  // built once per workspace
-            HIP_TRY(hipMalloc(&w->comp_hash, CH_SLOTS * sizeof(uint4)));
-            HIP_TRY(hipMemsetAsync(w->comp_hash, 0, CH_SLOTS * sizeof(uint4), st));
-            k_comp_hash_build<><<<(AK_UT_NCOMP + 255) / 256, 256, 0, st>>>(w->comp_hash);
-            HIP_TRY(hipGetLastError());
-        }
-        tfb.comp_hash = w->comp_hash;
-        // (no more waves than rows: a small call dispatches a block or two)
-        const unsigned lgrid = (unsigned)std::min<uint64_t>(ngrid, (a0.n + RT_NFC_BLOCK / 64 - 1) / (RT_NFC_BLOCK / 64));
-        k_rows_nfc<OPS><<<lgrid, RT_NFC_BLOCK, 0, st>>>(tfb, ofb, w->rnfc_buf, w->fb3, w->tile_misc + 5);
+        k_rows_nfc<OPS><<<lgrid, RT_NFC_BLOCK, 0, st>>>(tfb, ofb, w->rnfc_buf, w->fb3, w->tile_misc + TM_PASSON);
         HIP_TRY(hipGetLastError());
         AK_PROF(AK_PROF_FALLBACK_WAVE, true, st);
-        tfb.fb_list = w->fb3;
-        tfb.fb_count = w->tile_misc + 5;
-    } else {  // every fallback row goes on (ak_ws_fallback_detail)
-        HIP_TRY(hipMemcpyAsync(w->tile_misc + 5, w->tile_misc, 4, hipMemcpyDeviceToDevice, st));
+        fallback_wave_passed(w, tfb);
     }
     AK_PROF(AK_PROF_EMIT_SLOW, false, st);
     static std::atomic<int> fb_bpc{0};
@@ -242,7 +184,7 @@ int launch_rows_tiles(int ops, AkWs *w, const RowArgs &a0, int matras, const Row
         if (f.run_offs) HIP_TRY(hipMemsetAsync(f.run_offs, 0, 8, st));
         return AK_OK;
     }
-    int rc = ws_reserve(w, a0.n);
+    int rc = ws_reserve(w, a0.n, st);
     if (rc) return rc;
     uint64_t nbytes = 0;  // one 8-byte read-back sizes the staging areas
     if ((rc = ws_total_bytes(w, a0.offs, a0.n, st, &nbytes))) return rc;
@@ -255,14 +197,7 @@ int launch_rows_tiles(int ops, AkWs *w, const RowArgs &a0, int matras, const Row
     const uint64_t half8 = (nm ? A8 : 0) + (sw ? A32 : 0), half32 = (sg ? A32 : 0) + (sw ? A32 : 0);
     if ((rc = ws_stage_reserve(w, 2 * half32 + 64, st))) return rc;
     if ((rc = ws_stage8_reserve(w, 2 * half8 + 64, st))) return rc;
-    if (w->cap_acounts < 2 * a0.n) {
-        HIP_TRY(hipStreamSynchronize(st));
-        (void)hipFree(w->acounts);
-        w->acounts = nullptr;
-        w->cap_acounts = 0;
-        HIP_TRY(hipMalloc(&w->acounts, 2 * a0.n * 4));
-        w->cap_acounts = 2 * a0.n;
-    }
+    if ((rc = ws_acounts_reserve(w, a0.n, st))) return rc;
     RowsOut o;
     memset(&o, 0, sizeof(o));
     o.norm = w->stage8;

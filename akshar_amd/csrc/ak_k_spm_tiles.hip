@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "ak_internal.h"
+#include "ak_launch.h"
 #include "ak_small.h"
 #include "ak_tile_spm.h"
 
@@ -253,108 +254,43 @@ __global__ __launch_bounds__(256) void k_unit_copy_spm(const uint32_t *__restric
     }
 }
 
-static std::atomic<int> g_spm_blocks_per_cu{0};  // occupancy (same gfx950 part on every device; idempotent store)
-
 int launch_spm_tiles(AkWs *w, const RowArgs &a0, uint64_t *out_offs, hipStream_t st) {
     if (a0.n == 0) {
         HIP_TRY(hipMemsetAsync(out_offs, 0, 8, st));
         return AK_OK;
     }
-    int rc = ws_reserve(w, a0.n);
+    int rc = ws_reserve(w, a0.n, st);
     if (rc) return rc;
     uint64_t nbytes = 0;  // one 8-byte read-back sizes the staging area
     if ((rc = ws_total_bytes(w, a0.offs, a0.n, st, &nbytes))) return rc;
     // two halves: the tile kernel's unit runs, then the fallback rows' slots
     const uint64_t half = SPM_T_MUL * nbytes + SPM_T_ADD * a0.n + 64;
-    rc = ws_stage_reserve(w, 2 * half, st);
-    if (rc) return rc;
-    const int R = w->tile_rows;
-    const uint64_t ntiles = (a0.n + TILE_UNIT - 1) / TILE_UNIT;  // units of the work queue (ak_tile.h tile_first_unit)
-    if ((rc = ws_unit_fb_reserve(w, ntiles))) return rc;
-    if (w->cap_unit_len < ntiles) {
-        (void)hipFree(w->unit_len);
-        w->unit_len = nullptr;
-        w->cap_unit_len = 0;
-        HIP_TRY(hipMalloc(&w->unit_len, ntiles * 4));
-        w->cap_unit_len = ntiles;
-    }
-    if (w->cap_row_span < a0.n) {
-        (void)hipFree(w->row_span);
-        w->row_span = nullptr;
-        w->cap_row_span = 0;
-        HIP_TRY(hipMalloc(&w->row_span, a0.n * 4));
-        w->cap_row_span = a0.n;
-    }
-    if (!w->tile_misc) {  // [0] fb count, [1] overflow flag, [2] fb2 count, [3] the unit queue
-        HIP_TRY(hipMalloc(&w->tile_misc, 64 * 4));
-        HIP_TRY(hipMemsetAsync(w->tile_misc, 0, 64 * 4, st));
-    }
-    if (g_prof_passes && !w->tile_passprof) {
-        HIP_TRY(hipMalloc(&w->tile_passprof, T_NPROF * 8));
-        HIP_TRY(hipMemsetAsync(w->tile_passprof, 0, T_NPROF * 8, st));
-    }
-    if (!g_spm_blocks_per_cu.load(std::memory_order_relaxed)) {
-        int b = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_spm_tiles<3, false>, SPM_TILE_BLOCK, 0));
-        g_spm_blocks_per_cu.store(std::max(1, b), std::memory_order_relaxed);
-    }
-    if (w->cap_fb2 < a0.n) {
-        (void)hipFree(w->fb2);
-        w->fb2 = nullptr;
-        HIP_TRY(hipMalloc(&w->fb2, a0.n * 4));
-        w->cap_fb2 = a0.n;
-    }
-    if (w->cap_redo < a0.n) {
-        (void)hipFree(w->redo);
-        w->redo = nullptr;
-        HIP_TRY(hipMalloc(&w->redo, a0.n * 4));
-        w->cap_redo = a0.n;
-    }
-    TileArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    ta.ra = a0;
+    if ((rc = ws_stage_reserve(w, 2 * half, st))) return rc;
+    if ((rc = tile_ws_prepare(w, a0.n, st))) return rc;
+    if ((rc = ws_grow(w->row_span, w->cap_row_span, a0.n, st))) return rc;
+    if ((rc = ws_grow(w->redo, w->cap_redo, a0.n, st))) return rc;
+    const uint64_t ntiles = (a0.n + TILE_UNIT - 1) / TILE_UNIT;
+    static std::atomic<int> tile_bpc{0};
+    const unsigned grid = tile_grid(k_spm_tiles<3, false>, SPM_TILE_BLOCK, tile_bpc, ntiles, "AK_SPM_BPC");
+    // the word pools: SP_CAP entries per wave slot of the tile grid (the fallback waves use none)
+    if ((rc = tile_pool_reserve(w, st, (uint64_t)grid * (SPM_TILE_BLOCK / 64), 0, SP_CAP))) return rc;
+    TileArgs ta = tile_args_common(w, a0, ntiles);
     ta.ra.out = w->stage;
     ta.ra.cap = half;
-    ta.unit_fb = w->unit_fb;
-    ta.ra.out_offs = nullptr;
     ta.counts = w->counts;
-    ta.fb_list = w->slow_list;
-    ta.fb_count = w->tile_misc;
-    ta.err = w->tile_misc + 1;
-    ta.fb2_list = w->fb2;
-    ta.fb2_count = w->tile_misc + 2;
-    ta.next_unit = w->tile_misc + 3;
-    // a small launch keeps every word in its tile; so does the opt-in word cache (AK_SWC, tile variant)
-    if (a0.n < ta.ra.spm.pool_rows || ta.ra.spm.wc) ta.ra.spm.pool_ok = 0;
-    ta.redo_list = w->redo;
-    ta.redo_count = w->tile_misc + 4;
-    ta.redo_passon = w->tile_misc + 7;
-    ta.passprof = g_prof_passes ? w->tile_passprof : nullptr;
-    ta.ntiles = ntiles;
-    ta.rows = R;
-    // fallback count, overflow flag (ak_ws_check reports this call's), second fallback count, the
-    // unit queue, the word pool's redo count, k_spm_nfc's pass-on count = 0; [6] = 1: this launch is
-    // SentencePiece (ak_ws_fallback_detail); the counters; the units' fallback masks, OR-ed into (a
-    // pooled word may add a row to a finished unit): one launch (k_tile_init)
-    static_assert(CTR_N <= 256, "k_tile_init's first block clears the counters");
-    k_tile_init<><<<tile_init_grid(ntiles), 256, 0, st>>>(w->tile_misc, 8, 1u, w->ctr, CTR_N, w->unit_fb, ntiles);
-    HIP_TRY(hipGetLastError());
-    const uint64_t wpb = SPM_TILE_BLOCK / 64;
-    int bpc = g_spm_blocks_per_cu.load(std::memory_order_relaxed);
-    if (const char *e = getenv("AK_SPM_BPC")) bpc = std::max(1, std::min(bpc, atoi(e)));  // development aid
-    const unsigned grid = (unsigned)std::min<uint64_t>((ntiles + wpb - 1) / wpb, (uint64_t)num_cus() * (uint64_t)bpc);
-    // the waves' word pools: SP_CAP entries per wave slot of the grid (shared with the BPE merge pools)
-    const uint64_t pool_entries = (uint64_t)grid * wpb * SP_CAP;
-    if (w->cap_bpool < pool_entries) {
-        (void)hipFree(w->bpool);
-        w->bpool = nullptr;
-        w->cap_bpool = 0;
-        HIP_TRY(hipMalloc(&w->bpool, pool_entries * sizeof(uint4)));
-        w->cap_bpool = pool_entries;
-    }
+    ta.rows = w->tile_rows;
     ta.pool = w->bpool;
     ta.unit_len = w->unit_len;
     ta.row_span = w->row_span;
+    // a small launch keeps every word in its tile; so does the opt-in word cache (AK_SWC, tile variant)
+    if (a0.n < ta.ra.spm.pool_rows || ta.ra.spm.wc) ta.ra.spm.pool_ok = 0;
+    ta.redo_list = w->redo;
+    ta.redo_count = w->tile_misc + TM_REDO;
+    ta.redo_passon = w->tile_misc + TM_REDO_PASSON;
+    // the per-launch words, TM_SPM = 1, the counters, and the units' fallback masks, which are OR-ed
+    // into (a pooled word may add a row to a finished unit): one launch
+    k_tile_init<><<<tile_init_grid(ntiles), 256, 0, st>>>(w->tile_misc, TM_N, 1u, w->ctr, CTR_N, w->unit_fb, ntiles);
+    HIP_TRY(hipGetLastError());
     AK_PROF(AK_PROF_SPM_TILES, false, st);
     if (ta.ra.spm.pool_ok) k_spm_tiles<3, true><<<grid, SPM_TILE_BLOCK, 0, st>>>(ta);
     else k_spm_tiles<3, false><<<grid, SPM_TILE_BLOCK, 0, st>>>(ta);
@@ -363,43 +299,19 @@ int launch_spm_tiles(AkWs *w, const RowArgs &a0, uint64_t *out_offs, hipStream_t
     AK_PROF(AK_PROF_FALLBACK_WAVE, false, st);
     TileArgs tfb = ta;
     tfb.ra.out = w->stage + half;
-    tfb.ra.cap = half;
     static_assert(SPM_REDO_BLOCK == SPM_NFC_BLOCK, "k_spm_redo and k_spm_nfc share the epoch buffers");
-    const unsigned ngrid = (unsigned)num_cus();
-    const uint64_t nw = (uint64_t)ngrid * (SPM_NFC_BLOCK / 64);
-    if (w->cap_nfc < nw) {
-        (void)hipFree(w->nfc_buf);
-        w->nfc_buf = nullptr;
-        w->cap_nfc = 0;
-        HIP_TRY(hipMalloc(&w->nfc_buf, nw * NE_BYTES));
-        w->cap_nfc = nw;
-    }
     if (ta.ra.spm.pool_ok) {  // (only the pooled variant sends rows back: a small launch skips it)
-        k_spm_redo<3><<<ngrid, SPM_REDO_BLOCK, 0, st>>>(tfb, w->nfc_buf);
+        if ((rc = ws_grow(w->nfc_buf, w->cap_nfc, fallback_waves(SPM_REDO_BLOCK), st, GROW_EXACT, NE_BYTES))) return rc;
+        k_spm_redo<3><<<(unsigned)num_cus(), SPM_REDO_BLOCK, 0, st>>>(tfb, w->nfc_buf);
         HIP_TRY(hipGetLastError());
     }
-    if (!getenv("AK_NO_NFC_WAVE")) {  // (development aid: the one-lane path for every fallback row)
-        if (w->cap_fb3 < a0.n) {
-            (void)hipFree(w->fb3);
-            w->fb3 = nullptr;
-            HIP_TRY(hipMalloc(&w->fb3, a0.n * 4));
-            w->cap_fb3 = a0.n;
-        }
-        if (!w->comp_hash) {  // built once per workspace
-            HIP_TRY(hipMalloc(&w->comp_hash, CH_SLOTS * sizeof(uint4)));
-            HIP_TRY(hipMemsetAsync(w->comp_hash, 0, CH_SLOTS * sizeof(uint4), st));
-            k_comp_hash_build<><<<(AK_UT_NCOMP + 255) / 256, 256, 0, st>>>(w->comp_hash);
-            HIP_TRY(hipGetLastError());
-        }
-        tfb.comp_hash = w->comp_hash;
-        // (no more waves than rows: a small call dispatches a block or two of the 156 KB kernel)
-        const unsigned lgrid = (unsigned)std::min<uint64_t>(ngrid, (a0.n + SPM_NFC_BLOCK / 64 - 1) / (SPM_NFC_BLOCK / 64));
-        k_spm_nfc<3><<<lgrid, SPM_NFC_BLOCK, 0, st>>>(tfb, w->nfc_buf, w->fb3, w->tile_misc + 5);
+    unsigned lgrid = 0;  // (after k_spm_redo: it appends to the fallback list)
+    if ((rc = fallback_wave_prepare(w, st, a0.n, SPM_NFC_BLOCK, NE_BYTES, w->nfc_buf, w->cap_nfc, k_comp_hash_build<>, tfb, &lgrid)))
+        return rc;
+    if (lgrid) {
+        k_spm_nfc<3><<<lgrid, SPM_NFC_BLOCK, 0, st>>>(tfb, w->nfc_buf, w->fb3, w->tile_misc + TM_PASSON);
         HIP_TRY(hipGetLastError());
-        tfb.fb_list = w->fb3;
-        tfb.fb_count = w->tile_misc + 5;
-    } else {  // every fallback row goes on (ak_ws_fallback_detail)
-        HIP_TRY(hipMemcpyAsync(w->tile_misc + 5, w->tile_misc, 4, hipMemcpyDeviceToDevice, st));
+        fallback_wave_passed(w, tfb);
     }
     AK_PROF(AK_PROF_FALLBACK_WAVE, true, st);
     AK_PROF(AK_PROF_EMIT_SLOW, false, st);
@@ -416,18 +328,15 @@ int launch_spm_tiles(AkWs *w, const RowArgs &a0, uint64_t *out_offs, hipStream_t
     if (rc) return rc;
     AK_PROF(AK_PROF_EMIT_SLOW, true, st);
     AK_PROF(AK_PROF_SCAN, false, st);
-    rc = scan_counts(w, a0.n, out_offs, st);
-    if (rc) return rc;
+    if ((rc = scan_counts(w, a0.n, out_offs, st))) return rc;
     AK_PROF(AK_PROF_SCAN, true, st);
     AK_PROF(AK_PROF_COPY, false, st);
-    {
-        const unsigned cgrid = (unsigned)std::min<uint64_t>((ntiles + 3) / 4, (uint64_t)num_cus() * 8);
-        k_unit_copy_spm<<<cgrid, 256, 0, st>>>(w->stage, w->stage + half, a0.offs, out_offs, w->unit_fb, w->unit_len,
-                                               w->row_span, a0.n, (uint32_t *)a0.out, a0.cap, half);
-        HIP_TRY(hipGetLastError());
-    }
+    const unsigned cgrid = (unsigned)std::min<uint64_t>((ntiles + 3) / 4, (uint64_t)num_cus() * 8);
+    k_unit_copy_spm<<<cgrid, 256, 0, st>>>(w->stage, w->stage + half, a0.offs, out_offs, w->unit_fb, w->unit_len,
+                                           w->row_span, a0.n, (uint32_t *)a0.out, a0.cap, half);
+    HIP_TRY(hipGetLastError());
     AK_PROF(AK_PROF_COPY, true, st);
-    return rc;
+    return AK_OK;
 }
 
 }  // namespace ak
