@@ -567,17 +567,10 @@ static int64_t rows_tiles_run(int matras, const uint8_t *in, const uint64_t *off
     o.cnt_norm = cn.data(); o.cnt_seg = cs.data(); o.cnt_runs = cr.data(); o.matras = matras;
     RowsOut ofb = o;
     ofb.norm = o.norm + h8; ofb.seg = o.seg + h32; ofb.runs = o.runs + h32; ofb.labels = o.labels + h32;
-    RowsWaveMem *M = new RowsWaveMem();
-    EmuWave W;
-    std::vector<std::thread> th;
-    for (int lane = 0; lane < 64; ++lane)
-        th.emplace_back([&, lane] {
-            t_lane = lane;
-            t_wave = &W;
-            rows_tiles_wave<OPS>(ta, o, hot_tab, sc_tab, *M, 0, 1);
-        });
-    for (auto &x : th) x.join();
-    delete M;
+    {  // g_waves emulated waves on the one unit queue, as the launcher's
+        std::vector<RowsWaveMem> M(g_waves);
+        run_waves([&](int w) { rows_tiles_wave<OPS>(ta, o, hot_tab, sc_tab, M[w], (uint32_t)w, (uint32_t)g_waves); });
+    }
     if (err) return -1;
     g_last_fb = fbn;
     // fallback rows as k_rows_nfc: the waves' epochs (NFC, rows_tile<OPS, NFCD>, the rows' slots);

@@ -157,9 +157,9 @@ def spm_tiles(model, buf, offs, flags=3, rows=4, waves=1):
     return out[:tot], oo, st[:n]
 
 
-def rows_tiles(ops, buf, offs, matras=False, rows=16):
-    """Tile-cooperative normalize (1) / segment (2) / switches (4) / analyze (7) on one emulated wave
-    -> dict of (values, offsets) per op."""
+def rows_tiles(ops, buf, offs, matras=False, rows=16, waves=None):
+    """Tile-cooperative normalize (1) / segment (2) / switches (4) / analyze (7) on `waves` emulated
+    waves sharing the unit queue (None: as set by emu_set_waves) -> dict of (values, offsets) per op."""
     buf = pad(buf)
     offs = np.ascontiguousarray(offs, dtype=np.uint64)
     n = len(offs) - 1
@@ -170,11 +170,15 @@ def rows_tiles(ops, buf, offs, matras=False, rows=16):
     labels = np.zeros(nb + n + 64, np.uint8)
     no, so, ro = (np.zeros(n + 1, np.uint64) for _ in range(3))
     st = np.zeros(max(n, 1), np.uint8)
+    if waves is not None:
+        lib().emu_set_waves(waves)
     rc = lib().emu_rows_tiles(ops, int(matras), buf.ctypes.data, offs.ctypes.data, n, norm.ctypes.data, no.ctypes.data,
                               seg.ctypes.data, so.ctypes.data, runs.ctypes.data, labels.ctypes.data, ro.ctypes.data,
                               st.ctypes.data, rows)
+    if waves is not None:
+        lib().emu_set_waves(1)
     assert rc == 0, rc
-    return {"norm": (norm[:int(no[-1])], no), "seg": (seg[:int(so[-1])], so),
+    return {"status": st[:n], "norm": (norm[:int(no[-1])], no), "seg": (seg[:int(so[-1])], so),
             "runs": (runs[:int(ro[-1])], labels[:int(ro[-1])], ro)}
 
 

@@ -101,6 +101,27 @@ def test_spm_near_tie_rows(spm_model):
         assert np.array_equal(ids.astype(np.int64), want.astype(np.int64))
 
 
+def test_step_edge_rows(spm_model):
+    """The oracle equals the reference on every valid row of tests/rows_edge_rows.py (the tile kernels'
+    step edges and limits; tools/gen_golden_rows_edges.py): normalize, segment in both matras modes,
+    switches, and SentencePiece on the rows built for it."""
+    from tests import rows_edge_rows as R
+    for name, rows in (("rows", R.all_rows()), ("nfc", R.nfc_rows()), ("spm", R.spm_rows())):
+        want, _ = R.golden(name)
+        idx = sorted(want)
+        assert idx == [i for i, r in enumerate(rows) if R.is_valid(r)] and len(idx) > 100
+        packed = O.pack([want[i]["text"] for i in idx])
+        recs = [want[i] for i in idx]
+        assert [r["i"] for r, g in zip(recs, rows_u8(*O.normalize_batch(*packed, flags=3))) if g != r["norm"]] == []
+        for matras, key in ((False, "ak"), (True, "ak_m")):
+            got = [ends_to_lens(e) for e in rows_ints(*O.segment_batch(*packed, flags=3, matras=matras))]
+            assert [r["i"] for r, g in zip(recs, got) if g != r[key]] == []
+        assert [r["i"] for r, g in zip(recs, rows_runs(*O.switches_batch(*packed, flags=3))) if g != r["sw"]] == []
+        if name == "spm":
+            got = rows_ints(*O.OracleSPM(spm_model).encode_batch(*packed))
+            assert [r["i"] for r, g in zip(recs, got) if g != r["spm"]] == []
+
+
 def test_golden_covers_edge_cases(golden):
     sets = {r["set"] for r in golden}
     assert {"corpus", "adversarial", "devanagari", "hinglish", "fuzz", "alphabet", "long"} <= sets
