@@ -29,6 +29,9 @@ AK_PAD_LEFT = 1
 AK_TRUNC_LEFT = 2
 AK_DENSE_I64 = 4
 AK_PACK_DROP_LAST = 8
+# ak_ids_window_offs / ak_ids_windows flags (with AK_PAD_LEFT and AK_DENSE_I64)
+AK_WIN_FIXED_LAST = 16
+AK_WIN_LONGEST_FIRST = 32
 AK_ROW_BAD_UTF8 = 1
 AK_ROW_LIMIT = 4
 AK_TILE_PASSES = ("pre", "stage_decode_nfc_map", "elong_ws_pretok", "pretoken_cache", "pretoken_starts", "merge_or_viterbi",
@@ -85,6 +88,8 @@ SIGNATURES = {
     "ak_ids_pad": (I32, [P, P, U64, U32, ctypes.c_int32, U32, U32, I32, P, U64, P, P, P]),
     "ak_ids_pack": (I32, [P, P, U64, U32, ctypes.c_int32, ctypes.c_int32, I32, P, P, P, U64, P]),
     "ak_ids_pack_blocks": (U64, [U64, U64, I32, U32, I32]),
+    "ak_ids_window_offs": (I32, [P, P, P, U64, U32, U32, U32, U32, U32, I32, P, P]),
+    "ak_ids_windows": (I32, [P, P, P, P, U64, P, U32, U32, U32, U32, U32, ctypes.c_int32, I32, P, U64, P, P, P, P, P, P]),
     "ak_normalize_cap": (U64, [U64, U64]),
     "ak_segment_cap": (U64, [U64, U64]),
     "ak_bpe_encode_cap": (U64, [U64, U64]),

@@ -11,50 +11,12 @@
 // rows (a 64-bit division / a binary search over the row starts) is paid once per wave, not per chunk.
 // Every element index is 64-bit: n x width passes 2^32 at the corpus workload's sizes. No workspace,
 // no read-back, one launch per call.
-#include "ak_internal.h"
-#include "ak_wave.h"
+#include "ak_dense.h"
 
 namespace ak {
 
-constexpr int DENSE_BLOCK = 256;
-constexpr int DENSE_WAVES = DENSE_BLOCK / 64;
-constexpr uint32_t DENSE_VEC = 4;                 // output elements per lane and step
-constexpr uint32_t DENSE_CHUNK = 64 * DENSE_VEC;  // output elements per wave and step
-
 constexpr int VEC_OUT = 1;   // out (and pos, doc) are 16-byte aligned: whole-lane vector stores
 constexpr int VEC_MASK = 2;  // mask is 4-byte aligned
-
-// the 4 elements of a lane at a[e..e+3]: one vector store per 16 bytes where the array's alignment
-// allows (vec) and all 4 lie below `total`, element stores otherwise; nothing at or past `total`
-template <typename T>
-__device__ __forceinline__ void put4(T *a, uint64_t e, uint64_t total, const int32_t (&v)[DENSE_VEC], bool vec) {
-    if (vec && e + DENSE_VEC <= total) {
-        if constexpr (sizeof(T) == 4) {
-            *reinterpret_cast<int4 *>(a + e) = make_int4(v[0], v[1], v[2], v[3]);
-        } else if constexpr (sizeof(T) == 8) {
-            longlong2 *q = reinterpret_cast<longlong2 *>(a + e);
-            q[0] = make_longlong2(v[0], v[1]);
-            q[1] = make_longlong2(v[2], v[3]);
-        } else {
-            *reinterpret_cast<uint32_t *>(a + e) = (uint32_t)v[0] | (uint32_t)v[1] << 8 | (uint32_t)v[2] << 16 | (uint32_t)v[3] << 24;
-        }
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < DENSE_VEC; ++k)
-            if (e + k < total) a[e + k] = (T)v[k];
-    }
-}
-
-// the chunks [*ch, *end) of this wave: a contiguous span, the same number for every wave
-__device__ __forceinline__ bool wave_span(uint64_t total, uint64_t *ch, uint64_t *end) {
-    const uint64_t nw = (uint64_t)gridDim.x * DENSE_WAVES;
-    const uint64_t wv = (uint64_t)blockIdx.x * DENSE_WAVES + (threadIdx.x >> 6);
-    const uint64_t chunks = (total + DENSE_CHUNK - 1) / DENSE_CHUNK;
-    const uint64_t per = (chunks + nw - 1) / nw;
-    *ch = wv * per;
-    *end = *ch + per < chunks ? *ch + per : chunks;
-    return *ch < *end;
-}
 
 // total = rows x W output elements. Element (r, c): with L the row's length, kept = min(L, W) ids and
 // W - kept pads (left or right); a truncated row (L > W) keeps its first h and last t ids and W - h - t
@@ -199,13 +161,6 @@ __global__ __launch_bounds__(DENSE_BLOCK) void k_ids_pack(const int32_t *ids, co
         rb = w_bcast(last, 63);
     }
 }
-
-static unsigned dense_grid(uint64_t elems) {
-    const uint64_t want = (elems + (uint64_t)DENSE_CHUNK * DENSE_WAVES - 1) / ((uint64_t)DENSE_CHUNK * DENSE_WAVES);
-    return (unsigned)std::min<uint64_t>(std::max<uint64_t>(want, 1), (uint64_t)num_cus() * 8);
-}
-
-static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 }  // namespace ak
 

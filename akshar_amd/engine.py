@@ -575,8 +575,76 @@ def pack_ids(ids, offs, block, *, sep_id=None, pad_id=0, drop_last=False, dtype=
     return out, pos, doc
 
 
+def window_ids(ids, offs, width, pad_id, *, stride=0, keep_head=0, keep_tail=0, fixed=None, fixed_cap=None,
+               fixed_last=False, longest_first=False, padding_side="right", dtype=torch.int32, max_windows=None):
+    """Ragged device id rows -> sliding windows of `width` ids on the device, on the current stream
+    (include/akshar.h ak_ids_window_offs + ak_ids_windows): HF tokenizers' enable_truncation(width, stride)
+    with its overflow encodings. A row whose body (the ids between its keep_head and keep_tail template
+    ids) does not fit yields further windows that overlap by `stride` body ids, each with the row's head
+    and tail ids. fixed = (ids, offs) gives every row a partner row that is repeated in every window: in
+    front of the sliding part (HF "only_second"), or behind it with fixed_last ("only_first"); a partner
+    longer than fixed_cap is cut to it as pad_ids truncates (None: width - keep_head - keep_tail -
+    stride - 1, the largest legal value, so it is cut only when it has to be). longest_first (needs
+    fixed, stride 0): one window per row, partner then row, the longer body cut first as HF does.
+    Returns a dict of device tensors: input_ids [n_windows, width], attention_mask (bool),
+    token_type_ids (uint8: 0 on the first segment, 1 on the second), overflow_to_sample_mapping,
+    window_start (the window's first body id's index in the row's body), lengths (int32 [n_windows]) and
+    win_offs (int64 [n + 1]: the first window of every row). Sizing the outputs costs one 8-byte
+    read-back of win_offs[-1]; with max_windows there is none: the outputs have max_windows rows, those
+    from win_offs[-1] on are unwritten, and the caller reads win_offs."""
+    n = _check_ids(ids, offs)
+    dev = ids.device
+    width, stride, keep_head, keep_tail = int(width), int(stride), int(keep_head), int(keep_tail)
+    flags = _dense_dtype(dtype) | (_lib.AK_PAD_LEFT if _side("padding_side", padding_side) else 0)
+    if width <= 0 or stride < 0 or keep_head < 0 or keep_tail < 0:
+        raise ValueError("width must be positive; stride, keep_head and keep_tail must not be negative")
+    f_ids = f_offs = None
+    if fixed is not None:
+        f_ids, f_offs = fixed
+        if _check_ids(f_ids, f_offs) != n or f_ids.device != dev:
+            raise ValueError("fixed must hold one row per row of ids, on the same device")
+    elif fixed_cap or fixed_last or longest_first:
+        raise ValueError("fixed_cap, fixed_last and longest_first need the fixed rows")
+    if longest_first:
+        if stride or fixed_last:
+            raise ValueError("longest_first takes neither a stride nor fixed_last")
+        if width < 2 * (keep_head + keep_tail):
+            raise ValueError("width leaves no room for the two rows' template ids")
+        flags |= _lib.AK_WIN_LONGEST_FIRST
+        fixed_cap = 0
+    else:
+        room = width - keep_head - keep_tail - stride - 1  # what the fixed row may take at most
+        if room < 0:
+            raise ValueError("width - keep_head - keep_tail must exceed stride")
+        fixed_cap = (room if fixed is not None else 0) if fixed_cap is None else int(fixed_cap)
+        if not 0 <= fixed_cap <= room:
+            raise ValueError("fixed_cap must lie in 0..%d (width - keep_head - keep_tail - stride - 1)" % room)
+        flags |= _lib.AK_WIN_FIXED_LAST if fixed_last else 0
+    if max_windows is not None and int(max_windows) < 0:
+        raise ValueError("max_windows must not be negative")
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        win_offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        check(L.ak_ids_window_offs(workspace(dev.index), _ptr(offs), _ptr(f_offs), n, width, stride, keep_head, keep_tail,
+                                   fixed_cap, flags, _ptr(win_offs), _stream(dev)), "ak_ids_window_offs")
+        nw = int(win_offs[-1].item()) if max_windows is None else int(max_windows)
+        out = torch.empty((nw, width), dtype=dtype, device=dev)
+        mask = torch.empty((nw, width), dtype=torch.bool, device=dev)
+        types = torch.empty((nw, width), dtype=torch.uint8, device=dev)
+        sample, start, lengths = (torch.empty(nw, dtype=torch.int32, device=dev) for _ in range(3))
+        if n and nw:
+            one = torch.zeros(1, dtype=torch.int32, device=dev)  # all rows empty: a pointer nothing is read from
+            check(L.ak_ids_windows(_ptr(ids if ids.numel() else one), _ptr(offs),
+                                   None if fixed is None else _ptr(f_ids if f_ids.numel() else one), _ptr(f_offs), n,
+                                   _ptr(win_offs), width, stride, keep_head, keep_tail, fixed_cap, int(pad_id), flags,
+                                   _ptr(out), nw, _ptr(mask), _ptr(types), _ptr(sample), _ptr(start), _ptr(lengths),
+                                   _stream(dev)), "ak_ids_windows")
+    return {"input_ids": out, "attention_mask": mask, "token_type_ids": types, "overflow_to_sample_mapping": sample,
+            "window_start": start, "lengths": lengths, "win_offs": win_offs}
+
+
 __all__ = ["pack", "pack_host", "to_device", "normalize_batch", "segment_batch", "switches_batch", "BPE", "SPM",
-           "flags_of", "workspace", "AK_RAW", "pad_ids", "pack_ids"]
+           "flags_of", "workspace", "AK_RAW", "pad_ids", "pack_ids", "window_ids"]
 
 
 def profile_enable(on=True, passes=False):

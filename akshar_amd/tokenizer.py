@@ -129,6 +129,41 @@ class aksharTokenizer:
         out, pos, doc = engine.pack_ids(ids, oo, block_size, sep_id=sep_id, pad_id=pad_id, drop_last=drop_last)
         return {"input_ids": out, "position_ids": pos, "doc_ids": doc}
 
+    def encode_windows(self, texts, max_length: int, *, stride: int = 0, text_pair=None, truncation: str = "only_second",
+                       max_fixed_length: Optional[int] = None, padding_side: str = "right",
+                       pad_id: Optional[int] = None) -> dict:
+        """texts (and text_pair: each a list[str] or a (buf, offs) device pair) -> sliding windows of
+        max_length ids as device tensors (engine.window_ids: input_ids, attention_mask, token_type_ids,
+        overflow_to_sample_mapping, window_start, lengths, win_offs): HF tokenizers'
+        enable_truncation(max_length, stride) with its overflow encodings kept, padded to max_length.
+        With a pair, truncation names what slides: "only_second" repeats the text in front of every
+        window of its text_pair (a question and its context), "only_first" slides the text in front of
+        its repeated text_pair, "longest_first" (stride 0) gives one window per pair with the longer
+        side cut first. The repeated side is cut to max_fixed_length ids if given (at most
+        max_length - stride - 1 less the sliding side's <s> </s>, the default: larger values are
+        lowered to it), so it is cut only as far as it must be to leave the other side room. BPE rows keep their <s> ... </s> in every window.
+        Unlike HF, token_type_ids are 0 on the whole first segment and 1 on the whole second one."""
+        if self.model is None:
+            raise ValueError("need model for IDs")
+        if text_pair is not None and truncation not in ("only_second", "only_first", "longest_first"):
+            raise ValueError("truncation must be 'only_second', 'only_first' or 'longest_first', got %r" % (truncation,))
+        pad_id = self._pad_id(pad_id)
+        keep = 1 if self.model_type == "bpe" else 0
+        kw = dict(stride=stride, keep_head=keep, keep_tail=keep, padding_side=padding_side)
+        ids, oo = self._encode_rows(texts)
+        if text_pair is None:
+            return engine.window_ids(ids, oo, max_length, pad_id, **kw)
+        if max_fixed_length is not None:
+            if int(max_fixed_length) < 0:
+                raise ValueError("max_fixed_length must not be negative")
+            max_fixed_length = min(int(max_fixed_length), max(int(max_length) - 2 * keep - int(stride) - 1, 0))
+        pair = self._encode_rows(text_pair)
+        if truncation == "only_first":
+            return engine.window_ids(ids, oo, max_length, pad_id, fixed=pair, fixed_cap=max_fixed_length, fixed_last=True, **kw)
+        if truncation == "longest_first":
+            return engine.window_ids(*pair, max_length, pad_id, fixed=(ids, oo), longest_first=True, **kw)
+        return engine.window_ids(*pair, max_length, pad_id, fixed=(ids, oo), fixed_cap=max_fixed_length, **kw)
+
     def encode_batch(self, texts: List[str]) -> List[List[int]]:
         if self.model is None:
             raise ValueError("need model for IDs")

@@ -321,6 +321,54 @@ int ak_ids_pack(const int32_t *ids, const uint64_t *id_offs, uint64_t n, uint32_
                 int32_t pad_id, int flags, void *out, int32_t *pos, int32_t *doc, uint64_t cap_blocks, void *stream);
 uint64_t ak_ids_pack_blocks(uint64_t n_ids, uint64_t n, int has_sep, uint32_t block, int flags);
 
+/* Sliding windows and text pairs: what HF tokenizers' enable_truncation(width, stride) gives with its
+ * overflow encodings, for single sequences and for pairs. Input: a *sliding* stream (s_ids, s_offs[n+1])
+ * and optionally a *fixed* stream (f_ids, f_offs[n+1]) with one partner row per sliding row, both as the
+ * encode calls write them. A row has fewer than 2^32 ids (so have its windows: the counts are 32-bit).
+ * keep_head = h / keep_tail = t are the template's special tokens inside every row, as in ak_ids_pad
+ * ("<s> $A </s> <s> $B </s>": 1 and 1); a row shorter than h + t counts as h = t = 0. Per row, W = width:
+ *   F'   the fixed row, cut to fixed_cap ids if it is longer, as ak_ids_pad truncates on the right
+ *        (keeping h and t; a fixed_cap below h + t keeps the first fixed_cap ids); Lf' its length, 0
+ *        without a fixed stream.
+ *   C = W - Lf' - h - t ids of the sliding row's body (B ids) fit one window; consecutive windows start
+ *        step = C - stride body ids apart. The row has 1 window if B <= C, else 1 + ceil((B - C) / step);
+ *        an empty row has one too. Window k holds the row's h head ids, body[k step : min(k step + C, B)]
+ *        and its t tail ids; the last window may be shorter than the others.
+ *   The window's ids are F' then the sliding part (HF "only_second"), or the sliding part then F' with
+ *   AK_WIN_FIXED_LAST ("only_first"), padded with pad_id to W on the right, or on the left with AK_PAD_LEFT.
+ *   AK_WIN_LONGEST_FIRST (needs the fixed stream and stride == 0; fixed_cap is ignored): one window per
+ *   row, the fixed row then the sliding row, their bodies cut to n1 and n2 ids by HF's rule: whole if
+ *   they fit M = W - (h and t of both rows); else with n1 the shorter body and n2 the longer, n2 = n1 if
+ *   n1 > M, else max(n1, M - n1); if still n1 + n2 > M, n1 = M / 2 and n2 = n1 + M % 2 (equal bodies: the
+ *   fixed one is n1).
+ * ak_ids_window_offs writes win_offs[n+1], the index of every row's first window (win_offs[n]: the
+ * total; n == 0 writes win_offs[0] = 0). It uses the workspace and launches a count and a scan; there is
+ * no read-back. ak_ids_windows takes the same arguments and that win_offs, and writes, in one launch:
+ *   out       [n_windows x W] int32, or int64 with AK_DENSE_I64
+ *   mask      (optional) u8, out's shape: 1 for an id, 0 for padding
+ *   type_ids  (optional) u8, out's shape: 0 on the segment placed first and 1 on the one placed second,
+ *             their special tokens included; 0 on padding and everywhere without a fixed stream
+ *   sample    (optional) int32 [n_windows]: the window's row (HF overflow_to_sample_mapping)
+ *   start     (optional) int32 [n_windows]: k step, the body index of the window's first body id
+ *   lengths   (optional) int32 [n_windows]: ids in the window
+ * Nothing is stored at or past window cap_windows. n == 0 and cap_windows == 0 store nothing and launch
+ * nothing. AK_ERR_ARG, on the host before any device work: a NULL s_offs / win_offs / out / workspace,
+ * NULL s_ids with n > 0, f_ids without f_offs or the reverse, width == 0, a flag bit other than
+ * AK_PAD_LEFT | AK_DENSE_I64 | AK_WIN_* (AK_TRUNC_LEFT: windows slide rightwards only), fixed_cap != 0
+ * without a fixed stream, width - fixed_cap - h - t <= stride (so step >= 1 for every row),
+ * AK_WIN_LONGEST_FIRST without a fixed stream, with stride != 0, with width < 2 (h + t) or together with
+ * AK_WIN_FIXED_LAST. */
+#define AK_WIN_FIXED_LAST 16    /* the fixed segment follows the sliding one */
+#define AK_WIN_LONGEST_FIRST 32 /* one window per row, the longer body cut first */
+int ak_ids_window_offs(ak_ws *ws, const uint64_t *s_offs, const uint64_t *f_offs /*NULL: none*/, uint64_t n,
+                       uint32_t width, uint32_t stride, uint32_t keep_head, uint32_t keep_tail, uint32_t fixed_cap,
+                       int flags, uint64_t *win_offs, void *stream);
+int ak_ids_windows(const int32_t *s_ids, const uint64_t *s_offs, const int32_t *f_ids, const uint64_t *f_offs,
+                   uint64_t n, const uint64_t *win_offs, uint32_t width, uint32_t stride, uint32_t keep_head,
+                   uint32_t keep_tail, uint32_t fixed_cap, int32_t pad_id, int flags, void *out,
+                   uint64_t cap_windows, uint8_t *mask, uint8_t *type_ids, int32_t *sample, int32_t *start,
+                   int32_t *lengths, void *stream);
+
 /* Always-sufficient output capacities (elements) for n rows of total_bytes input bytes.
  * ak_bpe_encode_cap holds for flags 2 / 3; with clean_hinglish=False (flags 0 / 1) NFKC can
  * expand a char (U+FDFA: 3 bytes -> 18 code points): AK_BPE_NFKC_EXPANSION * total_bytes + 2n + 16. */
