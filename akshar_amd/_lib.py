@@ -90,6 +90,8 @@ SIGNATURES = {
     "ak_ids_pack_blocks": (U64, [U64, U64, I32, U32, I32]),
     "ak_ids_window_offs": (I32, [P, P, P, U64, U32, U32, U32, U32, U32, I32, P, P]),
     "ak_ids_windows": (I32, [P, P, P, P, U64, P, U32, U32, U32, U32, U32, ctypes.c_int32, I32, P, U64, P, P, P, P, P, P]),
+    "ak_ids_mlm": (I32, [P, P, U64, U32, U64, U64, U64, U64, U64, U64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                         ctypes.c_int32, P, U32, P, U32, I32, P, P, U64, P]),
     "ak_normalize_cap": (U64, [U64, U64]),
     "ak_segment_cap": (U64, [U64, U64]),
     "ak_bpe_encode_cap": (U64, [U64, U64]),

@@ -643,8 +643,76 @@ def window_ids(ids, offs, width, pad_id, *, stride=0, keep_head=0, keep_tail=0, 
             "window_start": start, "lengths": lengths, "win_offs": win_offs}
 
 
+def _threshold(name, p):
+    """A probability as the 33-bit threshold a 32-bit draw is compared with: min(2^32, round(p 2^32))."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("%s must lie in 0..1, got %r" % (name, p))
+    return min(1 << 32, int(round(p * (1 << 32))))
+
+
+def mask_ids(ids, attention_mask=None, *, mask_id, vocab_range, never=(), mlm_probability=0.15, mask_fraction=0.8,
+             random_fraction=0.1, seed=0, stream_id=0, elem_base=0, word_start=None, ignore_index=-100):
+    """A device id matrix [rows, width] (int32 or int64, as pad_ids / pack_ids return it) -> (inputs,
+    labels) of the same shape and dtype for masked-LM training, in one launch on the current stream
+    (include/akshar.h ak_ids_mlm). Every position where attention_mask (optional, bool / uint8) is set
+    and whose id is not in `never` (at most 8 ids: pad, bos, eos, ...) is selected with
+    mlm_probability; labels hold the id at the selected positions and ignore_index elsewhere; a selected
+    input becomes mask_id with mask_fraction, an id drawn evenly from vocab_range = (lo, hi), hi
+    excluded, with random_fraction, and stays otherwise. word_start (optional, a device uint8 tensor
+    with one entry per vocabulary id, nonzero where the id begins a word) selects whole words: an id
+    that begins none shares the selection of the nearest word start to its left.
+    The draws are Philox4x32-10 of (seed, stream_id, elem_base + the element's index): the same
+    arguments give the same result on every run, whatever torch's generators hold; another stream_id (an
+    epoch, a rank) gives an independent draw; elem_base continues a larger batch's numbering."""
+    t_select = _threshold("mlm_probability", mlm_probability)
+    t_mask = _threshold("mask_fraction", mask_fraction)
+    t_random = _threshold("random_fraction", random_fraction)
+    if float(mask_fraction) + float(random_fraction) > 1.0:
+        raise ValueError("mask_fraction + random_fraction must not exceed 1")
+    t_random = min(t_random, (1 << 32) - t_mask)  # the two roundings may add up to 2^32 + 1
+    lo, hi = (int(v) for v in vocab_range)
+    if not -(1 << 31) <= lo < hi <= (1 << 31) - 1:
+        raise ValueError("vocab_range must be (lo, hi) with lo < hi, both int32")
+    never = [int(v) for v in never]
+    if len(never) > 8:
+        raise ValueError("never takes at most 8 ids, got %d" % len(never))
+    mask_id, ignore_index = int(mask_id), int(ignore_index)
+    for name, v in [("mask_id", mask_id), ("ignore_index", ignore_index)] + [("never", v) for v in never]:
+        if not -(1 << 31) <= v < 1 << 31:
+            raise ValueError("%s must be int32, got %d" % (name, v))
+    for name, v in (("seed", seed), ("stream_id", stream_id), ("elem_base", elem_base)):
+        if not 0 <= int(v) < 1 << 64:
+            raise ValueError("%s must lie in 0..2^64-1" % name)
+    # the tensors (the values above are checked first: they need no device)
+    if ids.dim() != 2 or not ids.is_cuda or not ids.is_contiguous():
+        raise TypeError("ids must be a contiguous [rows, width] device tensor")
+    flags = _dense_dtype(ids.dtype)
+    dev = ids.device
+    rows, width = ids.shape
+    if width <= 0:
+        raise ValueError("width must be positive")
+    if attention_mask is not None:
+        _check_dense(attention_mask, "attention_mask", (torch.bool, torch.uint8), rows * width, dev)
+    n_vocab = 0
+    if word_start is not None:
+        if word_start.dim() != 1 or word_start.numel() == 0:
+            raise ValueError("word_start must hold one entry per vocabulary id")
+        _check_dense(word_start, "word_start", (torch.uint8, torch.bool), word_start.numel(), dev)
+        n_vocab = word_start.numel()
+    nev = (ctypes.c_int32 * max(len(never), 1))(*never)
+    with torch.cuda.device(dev):
+        out, labels = torch.empty_like(ids), torch.empty_like(ids)
+        if rows:
+            check(_lib.lib().ak_ids_mlm(_ptr(ids), _ptr(attention_mask), rows, width, int(seed), int(stream_id),
+                                        int(elem_base), t_select, t_mask, t_random, mask_id, lo, hi, ignore_index,
+                                        nev, len(never), _ptr(word_start), n_vocab, flags, _ptr(out), _ptr(labels), rows,
+                                        _stream(dev)), "ak_ids_mlm")
+    return out, labels
+
+
 __all__ = ["pack", "pack_host", "to_device", "normalize_batch", "segment_batch", "switches_batch", "BPE", "SPM",
-           "flags_of", "workspace", "AK_RAW", "pad_ids", "pack_ids", "window_ids"]
+           "flags_of", "workspace", "AK_RAW", "pad_ids", "pack_ids", "window_ids", "mask_ids"]
 
 
 def profile_enable(on=True, passes=False):

@@ -65,6 +65,9 @@ class BPEModel:
         # ids of "<pad>" / "</s>" for padded batches and packed blocks (None when the vocabulary has none)
         self.pad_id = self.vocab.get("<pad>")
         self.eos_id = self.vocab.get("</s>")
+        # "<mask>" / "<unk>" for masked-LM batches (encode_mlm), likewise
+        self.mask_id = self.vocab.get("<mask>")
+        self.unk_token_id = self.vocab.get("<unk>")
         # HF decode with no decoder configured: tokens joined by ' ' (special tokens skipped)
         self.special_ids = {int(a["id"]) for a in j.get("added_tokens", []) if a.get("special")}
         # AddedVocabulary: split the text on these before the normalizer (ak_bpe_set_added)
@@ -193,6 +196,9 @@ class SPMModel:
         # ids of "<pad>" / "</s>" for padded batches and packed blocks (None when the model has none)
         self.pad_id = self.piece_to_id.get(b"<pad>")
         self.eos_id = self.piece_to_id.get(b"</s>")
+        # "<mask>" / "<s>" for masked-LM batches (encode_mlm), likewise
+        self.mask_id = self.piece_to_id.get(b"<mask>")
+        self.bos_id = self.piece_to_id.get(b"<s>")
         # Fast path precondition: no piece carries U+2581 after its first character, so every
         # '▁' is a forced Viterbi boundary (SPM kernel).
         self.ws_boundary = all(b"\xe2\x96\x81" not in p[1:] for p, t in zip(pieces, types)

@@ -164,6 +164,56 @@ class aksharTokenizer:
             return engine.window_ids(*pair, max_length, pad_id, fixed=(ids, oo), longest_first=True, **kw)
         return engine.window_ids(*pair, max_length, pad_id, fixed=(ids, oo), fixed_cap=max_fixed_length, **kw)
 
+    def _word_start(self, dev):
+        """uint8 [vocab_size] on `dev`: 1 for the SentencePiece pieces that begin with U+2581 (a word's
+        first piece); built once per device and kept."""
+        cache = self.__dict__.setdefault("_word_start_cache", {})
+        if dev not in cache:
+            import torch
+            flags = np.fromiter((p.startswith(b"\xe2\x96\x81") for p in self.model.model.pieces), dtype=np.uint8,
+                                count=self.model.model.vocab_size)
+            cache[dev] = torch.from_numpy(flags).to(dev)
+        return cache[dev]
+
+    def encode_mlm(self, texts, max_length: int, *, mlm_probability: float = 0.15, seed: int = 0, stream_id: int = 0,
+                   whole_word: bool = False, mask_fraction: float = 0.8, random_fraction: float = 0.1,
+                   mask_id: Optional[int] = None, ignore_index: int = -100, padding_side: str = "right",
+                   truncation_side: str = "right", pad_id: Optional[int] = None) -> dict:
+        """texts (list[str] or a (buf, offs) device pair) -> {"input_ids" [n, max_length],
+        "attention_mask" bool, "labels", "lengths" int32 [n]} as device tensors: encode_padded's batch
+        masked for encoder pretraining (engine.mask_ids, BERT's rule): mlm_probability of the tokens
+        carry a label, and of those mask_fraction show the model's <mask>, random_fraction a random id
+        of the vocabulary and the rest themselves; every other label is ignore_index. Padding and the
+        model's <pad> <unk> <s> </s> <mask> are never selected. The same (seed, stream_id) gives the
+        same batch on every run; pass the epoch or the rank as stream_id for another draw.
+        whole_word (SentencePiece only): a word's pieces are selected together, a word beginning at
+        every piece that starts with U+2581. BPE ids carry no word boundaries (the Whitespace
+        pre-tokenizer drops them), so whole_word raises ValueError there."""
+        if self.model is None:
+            raise ValueError("need model for IDs")
+        m = self.model.model
+        mask_id = m.mask_id if mask_id is None else mask_id
+        if mask_id is None:
+            raise ValueError("the model has no <mask> token: pass mask_id")
+        if whole_word and self.model_type != "sentencepiece":
+            raise ValueError("whole_word needs a SentencePiece model: BPE ids carry no word boundaries")
+        pad_id = self._pad_id(pad_id)
+        if self.model_type == "bpe":
+            special = (pad_id, m.unk_token_id, m.bos, m.eos, mask_id)
+        else:
+            special = (pad_id, m.unk_id, m.bos_id, m.eos_id, mask_id)
+        never = sorted({int(v) for v in special if v is not None})
+        keep = 1 if self.model_type == "bpe" else 0
+        ids, oo = self._encode_rows(texts)
+        out, mask, lengths = engine.pad_ids(ids, oo, max_length, pad_id, padding_side=padding_side,
+                                            truncation_side=truncation_side, keep_head=keep, keep_tail=keep)
+        inputs, labels = engine.mask_ids(out, mask, mask_id=int(mask_id), vocab_range=(0, m.vocab_size), never=never,
+                                         mlm_probability=mlm_probability, mask_fraction=mask_fraction,
+                                         random_fraction=random_fraction, seed=seed, stream_id=stream_id,
+                                         word_start=self._word_start(out.device) if whole_word else None,
+                                         ignore_index=ignore_index)
+        return {"input_ids": inputs, "attention_mask": mask, "labels": labels, "lengths": lengths}
+
     def encode_batch(self, texts: List[str]) -> List[List[int]]:
         if self.model is None:
             raise ValueError("need model for IDs")

@@ -369,6 +369,40 @@ int ak_ids_windows(const int32_t *s_ids, const uint64_t *s_offs, const int32_t *
                    uint64_t cap_windows, uint8_t *mask, uint8_t *type_ids, int32_t *sample, int32_t *start,
                    int32_t *lengths, void *stream);
 
+/* Masked-LM batches (BERT's rule) from a dense id matrix, such as ak_ids_pad's: in, out and labels are
+ * [rows x width], row-major, int32, or int64 with AK_DENSE_I64; device pointers with no alignment
+ * requirement. One kernel launch on `stream`, no workspace, no read-back. Every step is unsigned
+ * 32 / 64-bit integer arithmetic, so a call reproduces bit for bit:
+ *   Element (r, c) has the 64-bit index e = elem_base + r width + c. Its draw is x0..x3 =
+ *   Philox4x32-10(counter (lo32(e), hi32(e), lo32(stream_id), hi32(stream_id)), key (lo32(seed),
+ *   hi32(seed))), with the published constants (multipliers 0xD2511F53, 0xCD9E8D57, Weyl increments
+ *   0x9E3779B9, 0xBB67AE85; the all-zero counter and key give 6627e8d5 e169c58d bc57ac4c 9b00dbd8).
+ *   An element is eligible when attn (optional, u8 [rows x width]) is NULL or attn[r, c] != 0, and its
+ *   id is not one of never[0 .. n_never) (a host pointer, n_never <= 8).
+ *   Leader: without word_start, the element itself. With word_start (optional, device, u8 [n_vocab]):
+ *   the nearest (r, c') with c' <= c at which the run of eligible elements that holds c begins, or at
+ *   which word_start[id] != 0; an id outside [0, n_vocab) counts as a word start. The search walks left
+ *   inside row r only: it stops at column 0, at an ineligible element (the leader is the column after
+ *   it) or at a flagged id.
+ *   Selected: eligible and x0 of the leader's draw < t_select (compared in 64 bits: t_select = 2^32
+ *   selects every eligible element).
+ *   labels[r, c] = the input id if selected, else ignore_index. out[r, c] = the input id if not
+ *   selected; if selected, by the element's own x1 and x2: mask_id if x1 < t_mask, else rand_lo +
+ *   (int32)(((uint64)x2 (uint32)(rand_hi - rand_lo)) >> 32) if x1 < t_mask + t_random, else the input id.
+ * Nothing is stored at or past row cap_rows. rows == 0 or cap_rows == 0 launches nothing. Calls over
+ * parts of one batch draw what one call over the whole batch draws when elem_base is the part's first
+ * element index. It works on ak_ids_pack's blocks as well, with sep_id and pad_id in never (a word or a
+ * selection then never looks across a separator, but rows are blocks, not documents).
+ * AK_ERR_ARG, on the host before any device work: NULL in, out or labels with rows > 0; width == 0; a
+ * threshold above 2^32, or t_mask + t_random > 2^32; rand_hi <= rand_lo with t_random > 0; n_never > 8,
+ * or never == NULL with n_never > 0; word_start with n_vocab == 0; a flag bit other than AK_DENSE_I64;
+ * out or labels equal to in, or out == labels (the leader search reads neighbours: no in-place). */
+int ak_ids_mlm(const void *in, const uint8_t *attn /*optional*/, uint64_t rows, uint32_t width, uint64_t seed,
+               uint64_t stream_id, uint64_t elem_base, uint64_t t_select, uint64_t t_mask, uint64_t t_random,
+               int32_t mask_id, int32_t rand_lo, int32_t rand_hi, int32_t ignore_index, const int32_t *never,
+               uint32_t n_never, const uint8_t *word_start /*optional*/, uint32_t n_vocab, int flags, void *out,
+               void *labels, uint64_t cap_rows, void *stream);
+
 /* Always-sufficient output capacities (elements) for n rows of total_bytes input bytes.
  * ak_bpe_encode_cap holds for flags 2 / 3; with clean_hinglish=False (flags 0 / 1) NFKC can
  * expand a char (U+FDFA: 3 bytes -> 18 code points): AK_BPE_NFKC_EXPANSION * total_bytes + 2n + 16. */
