@@ -32,6 +32,7 @@ AK_PACK_DROP_LAST = 8
 # ak_ids_window_offs / ak_ids_windows flags (with AK_PAD_LEFT and AK_DENSE_I64)
 AK_WIN_FIXED_LAST = 16
 AK_WIN_LONGEST_FIRST = 32
+AK_SPANS_MAX_WIDTH = 4096
 AK_ROW_BAD_UTF8 = 1
 AK_ROW_LIMIT = 4
 AK_TILE_PASSES = ("pre", "stage_decode_nfc_map", "elong_ws_pretok", "pretoken_cache", "pretoken_starts", "merge_or_viterbi",
@@ -92,6 +93,9 @@ SIGNATURES = {
     "ak_ids_windows": (I32, [P, P, P, P, U64, P, U32, U32, U32, U32, U32, ctypes.c_int32, I32, P, U64, P, P, P, P, P, P]),
     "ak_ids_mlm": (I32, [P, P, U64, U32, U64, U64, U64, U64, U64, U64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                          ctypes.c_int32, P, U32, P, U32, I32, P, P, U64, P]),
+    "ak_ids_spans": (I32, [P, P, U64, U32, U64, U64, U64, U64, U32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                           ctypes.c_int32, ctypes.c_int32, I32, P, U32, P, U32, P, P, P, U64, P]),
+    "ak_ids_spans_lengths": (I32, [U32, U64, U32, I32, ctypes.POINTER(U64)]),
     "ak_normalize_cap": (U64, [U64, U64]),
     "ak_segment_cap": (U64, [U64, U64]),
     "ak_bpe_encode_cap": (U64, [U64, U64]),

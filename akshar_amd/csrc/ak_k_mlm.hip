@@ -11,6 +11,7 @@
 // element accesses otherwise and in the chunk that straddles the capacity. Every element index is
 // 64-bit. A lane whose 4 elements are all ineligible (padding) skips the generator altogether.
 #include "ak_dense.h"
+#include "ak_philox.h"
 
 namespace ak {
 
@@ -28,28 +29,6 @@ struct MlmArgs {
     int32_t mask_id, rand_lo, ignore_index;
     int32_t never[MLM_NEVER];
 };
-
-struct Philox {
-    uint32_t x0, x1, x2, x3;
-};
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) of the counter
-// (lo32(e), hi32(e), lo32(stream_id), hi32(stream_id)) under the key (k0, k1)
-__device__ __forceinline__ Philox philox4x32_10(uint64_t e, uint64_t stream_id, uint32_t k0, uint32_t k1) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-    uint32_t c0 = (uint32_t)e, c1 = (uint32_t)(e >> 32), c2 = (uint32_t)stream_id, c3 = (uint32_t)(stream_id >> 32);
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint32_t h0 = __umulhi(M0, c0), l0 = M0 * c0, h1 = __umulhi(M1, c2), l1 = M1 * c2;
-        c0 = h1 ^ c1 ^ k0;
-        c1 = l1;
-        c2 = h0 ^ c3 ^ k1;
-        c3 = l0;
-        k0 += W0;
-        k1 += W1;
-    }
-    return Philox{c0, c1, c2, c3};
-}
 
 // the 4 elements of a lane from a[e..e+3]; those at or past `total` read as 0
 template <typename T>

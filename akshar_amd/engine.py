@@ -711,8 +711,108 @@ def mask_ids(ids, attention_mask=None, *, mask_id, vocab_range, never=(), mlm_pr
     return out, labels
 
 
+def _span_rates(noise_density, mean_span_length):
+    """(density_q32, mean_q16) as ak_ids_spans takes them."""
+    density_q32 = _threshold("noise_density", noise_density)
+    mean = float(mean_span_length)
+    if not 1.0 <= mean < 65536.0:
+        raise ValueError("mean_span_length must lie in 1..65535, got %r" % (mean_span_length,))
+    return density_q32, min((1 << 32) - 1, int(round(mean * 65536)))
+
+
+def span_lengths(L, *, noise_density=0.15, mean_span_length=3.0, eos=False):
+    """(N, S, in_len, tgt_len) of a row of L ids under span corruption (include/akshar.h
+    ak_ids_spans_lengths, host arithmetic): its noise tokens and spans, and the ids its inputs and its
+    targets take, the closing eos included if eos."""
+    density_q32, mean_q16 = _span_rates(noise_density, mean_span_length)
+    if not 0 <= int(L) < 1 << 32:
+        raise ValueError("L must lie in 0..2^32-1")
+    out = (ctypes.c_uint64 * 4)()
+    check(_lib.lib().ak_ids_spans_lengths(int(L), density_q32, mean_q16, int(bool(eos)), out), "ak_ids_spans_lengths")
+    return tuple(int(v) for v in out)
+
+
+def span_raw_length(inputs_length, *, noise_density=0.15, mean_span_length=3.0, eos=False):
+    """(L, tgt_len): the longest row, up to the AK_SPANS_MAX_WIDTH ids span_ids takes, whose corrupted
+    inputs fit inputs_length ids, and its targets' length (T5's compute_input_and_target_lengths): pack the
+    corpus into blocks of L ids and every batch is [n, inputs_length] and [n, tgt_len] without padding."""
+    inputs_length = int(inputs_length)
+    for L in range(_lib.AK_SPANS_MAX_WIDTH, -1, -1):
+        _, _, in_len, tgt_len = span_lengths(L, noise_density=noise_density, mean_span_length=mean_span_length, eos=eos)
+        if in_len <= inputs_length:
+            return L, tgt_len
+    raise ValueError("no row fits inputs_length = %d" % inputs_length)
+
+
+def span_ids(ids, lengths=None, *, noise_density=0.15, mean_span_length=3.0, sentinel_first, sentinel_step=-1, eos_id=None,
+             pad_id, label_pad=-100, in_width=None, tgt_width=None, seed=0, stream_id=0, elem_base=0, noise_mask=False,
+             n_sentinels=None):
+    """A device id matrix [rows, width] (int32 or int64, as pack_ids / pad_ids return it; width up to
+    4096) -> span-corruption batches for encoder-decoder pretraining (T5's objective), in one launch on
+    the current stream (include/akshar.h ak_ids_spans). Of the first lengths[r] ids of row r (lengths:
+    optional int32 [rows]; None: all) noise_density are noise, in spans of mean_span_length ids on average;
+    the counts depend on the length alone, which spans on the draw. Returns a dict of device tensors:
+    input_ids [rows, in_width] (the kept ids, every span replaced by one sentinel, then eos_id if given,
+    then pad_id), labels [rows, tgt_width] (every sentinel followed by its span, then eos_id, then
+    label_pad), input_lengths and label_lengths (int32 [rows]: what each row needs, whatever the widths)
+    and, with noise_mask, noise_mask (bool, ids' shape). Span i's sentinel is sentinel_first + i
+    sentinel_step: T5's are the last vocabulary ids counting down; sentinel_step 0 shows one id, such as
+    <mask>, for every span. n_sentinels (optional): how many sentinel ids the vocabulary reserves;
+    ValueError if a full row has more spans. The widths default to what a full row needs
+    (span_lengths(width)); a shorter width cuts the rows that need more, a longer one pads.
+    The draws are Philox4x32-10 of (seed, stream_id, elem_base + the element's index), as mask_ids':
+    reproducible whatever torch's generators hold; elem_base continues a larger batch's numbering."""
+    density_q32, mean_q16 = _span_rates(noise_density, mean_span_length)
+    if eos_id is not None and int(eos_id) < 0:
+        raise ValueError("eos_id must be a token id (or None for no eos)")
+    eos = -1 if eos_id is None else int(eos_id)
+    sentinel_first, sentinel_step, pad_id, label_pad = int(sentinel_first), int(sentinel_step), int(pad_id), int(label_pad)
+    for name, v in (("sentinel_first", sentinel_first), ("sentinel_step", sentinel_step), ("eos_id", eos), ("pad_id", pad_id),
+                    ("label_pad", label_pad)):
+        if not -(1 << 31) <= v < 1 << 31:
+            raise ValueError("%s must be int32, got %d" % (name, v))
+    for name, v in (("seed", seed), ("stream_id", stream_id), ("elem_base", elem_base)):
+        if not 0 <= int(v) < 1 << 64:
+            raise ValueError("%s must lie in 0..2^64-1" % name)
+    if ids.dim() != 2:
+        raise TypeError("ids must be a contiguous [rows, width] device tensor")
+    rows, width = ids.shape
+    if not 0 < width <= _lib.AK_SPANS_MAX_WIDTH:
+        raise ValueError("width must lie in 1..%d, got %d" % (_lib.AK_SPANS_MAX_WIDTH, width))
+    _, S, in_len, tgt_len = span_lengths(width, noise_density=noise_density, mean_span_length=mean_span_length,
+                                         eos=eos_id is not None)
+    if n_sentinels is not None and S > int(n_sentinels):
+        raise ValueError("a row of %d ids has %d spans, more than the %d sentinels" % (width, S, int(n_sentinels)))
+    in_width = in_len if in_width is None else int(in_width)
+    tgt_width = tgt_len if tgt_width is None else int(tgt_width)
+    if in_width <= 0 or tgt_width <= 0:
+        raise ValueError("in_width and tgt_width must be positive")
+    # the tensors (the values above are checked first: they need no device)
+    if not ids.is_cuda or not ids.is_contiguous():
+        raise TypeError("ids must be a contiguous [rows, width] device tensor")
+    flags = _dense_dtype(ids.dtype)
+    dev = ids.device
+    if lengths is not None:
+        _check_dense(lengths, "lengths", (torch.int32,), rows, dev)
+    with torch.cuda.device(dev):
+        inputs = torch.empty((rows, in_width), dtype=ids.dtype, device=dev)
+        labels = torch.empty((rows, tgt_width), dtype=ids.dtype, device=dev)
+        in_lengths, tgt_lengths = (torch.empty(rows, dtype=torch.int32, device=dev) for _ in range(2))
+        noise = torch.empty((rows, width), dtype=torch.bool, device=dev) if noise_mask else None
+        if rows:
+            check(_lib.lib().ak_ids_spans(_ptr(ids), _ptr(lengths), rows, width, int(seed), int(stream_id), int(elem_base),
+                                          density_q32, mean_q16, sentinel_first, sentinel_step, eos, pad_id, label_pad, flags,
+                                          _ptr(inputs), in_width, _ptr(labels), tgt_width, _ptr(in_lengths),
+                                          _ptr(tgt_lengths), _ptr(noise), rows, _stream(dev)), "ak_ids_spans")
+    res = {"input_ids": inputs, "labels": labels, "input_lengths": in_lengths, "label_lengths": tgt_lengths}
+    if noise_mask:
+        res["noise_mask"] = noise
+    return res
+
+
 __all__ = ["pack", "pack_host", "to_device", "normalize_batch", "segment_batch", "switches_batch", "BPE", "SPM",
-           "flags_of", "workspace", "AK_RAW", "pad_ids", "pack_ids", "window_ids", "mask_ids"]
+           "flags_of", "workspace", "AK_RAW", "pad_ids", "pack_ids", "window_ids", "mask_ids", "span_ids", "span_lengths",
+           "span_raw_length"]
 
 
 def profile_enable(on=True, passes=False):

@@ -214,6 +214,54 @@ class aksharTokenizer:
                                          ignore_index=ignore_index)
         return {"input_ids": inputs, "attention_mask": mask, "labels": labels, "lengths": lengths}
 
+    def encode_spans(self, texts, inputs_length: int, *, noise_density: float = 0.15, mean_span_length: float = 3.0,
+                     sentinel_first: Optional[int] = None, sentinel_step: Optional[int] = None, seed: int = 0,
+                     stream_id: int = 0, dtype=None, pad_id: Optional[int] = None) -> dict:
+        """texts (list[str] or a (buf, offs) device pair) -> {"input_ids" [n_blocks, inputs_length],
+        "labels" [n_blocks, label_length], "input_lengths", "label_lengths"} as device tensors:
+        span-corruption batches for encoder-decoder pretraining (T5's objective, engine.span_ids). The
+        rows' ids are packed (encode_blocks, its default separator, no partial last block) into blocks
+        of engine.span_raw_length(inputs_length) ids, the longest whose corrupted form fits
+        inputs_length, and every block is corrupted: noise_density of its ids in spans of
+        mean_span_length on average; the inputs show one sentinel per span and end in </s>, the labels
+        list every sentinel and its span, end in </s> and are padded with -100. By default every
+        sentinel is the model's <mask> (BART's text infilling: the shipped vocabularies reserve no
+        sentinel range). For T5's numbered sentinels pass sentinel_first (and sentinel_step, -1 if left
+        out) of a vocabulary that reserves the ids sentinel_first, sentinel_first + sentinel_step, ...;
+        ValueError if a block has more spans than ids lie between sentinel_first and the vocabulary's
+        end in that direction. pad_id defaults to the model's <pad>. The same (seed, stream_id) gives
+        the same batch on every run; pass the epoch or the rank as stream_id for another draw."""
+        import torch
+        if self.model is None:
+            raise ValueError("need model for IDs")
+        m = self.model.model
+        n_sentinels = None
+        if sentinel_first is None:
+            if m.mask_id is None:
+                raise ValueError("the model has no <mask> token: pass sentinel_first")
+            if sentinel_step not in (None, 0):
+                raise ValueError("sentinel_step needs sentinel_first: the default sentinel is <mask> for every span")
+            sentinel_first, sentinel_step = m.mask_id, 0
+        else:
+            sentinel_first = int(sentinel_first)
+            sentinel_step = -1 if sentinel_step is None else int(sentinel_step)
+            if sentinel_step < 0:  # the range runs down to id 0
+                n_sentinels = sentinel_first // -sentinel_step + 1 if sentinel_first >= 0 else 0
+            elif sentinel_step > 0:
+                n_sentinels = max(0, -(-(m.vocab_size - sentinel_first) // sentinel_step))
+        eos_id = m.eos if self.model_type == "bpe" else m.eos_id
+        block, _ = engine.span_raw_length(inputs_length, noise_density=noise_density, mean_span_length=mean_span_length,
+                                          eos=True)
+        if block < 2:
+            raise ValueError("inputs_length = %d leaves no room for a span" % int(inputs_length))
+        pad_id = self._pad_id(pad_id)
+        ids = self.encode_blocks(texts, block, pad_id=pad_id, drop_last=True)["input_ids"]
+        if dtype not in (None, torch.int32):
+            ids = ids.to(dtype)
+        return engine.span_ids(ids, noise_density=noise_density, mean_span_length=mean_span_length,
+                               sentinel_first=sentinel_first, sentinel_step=sentinel_step, eos_id=eos_id, pad_id=pad_id,
+                               in_width=int(inputs_length), seed=seed, stream_id=stream_id, n_sentinels=n_sentinels)
+
     def encode_batch(self, texts: List[str]) -> List[List[int]]:
         if self.model is None:
             raise ValueError("need model for IDs")

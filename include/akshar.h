@@ -403,6 +403,57 @@ int ak_ids_mlm(const void *in, const uint8_t *attn /*optional*/, uint64_t rows, 
                uint32_t n_never, const uint8_t *word_start /*optional*/, uint32_t n_vocab, int flags, void *out,
                void *labels, uint64_t cap_rows, void *stream);
 
+/* Span-corruption batches (T5's encoder-decoder objective) from a dense id matrix: `in` is [rows x width],
+ * row-major, int32, or int64 with AK_DENSE_I64, as ak_ids_pack (full blocks: AK_PACK_DROP_LAST) or
+ * ak_ids_pad write it; device pointers with no alignment requirement. One kernel launch on `stream`, no
+ * workspace, no read-back. Every step is unsigned integer arithmetic, so a call reproduces bit for bit.
+ *   Row r uses its first L = clamp(lengths[r], 0, width) ids (lengths: optional, device, int32 [rows];
+ *   NULL: L = width). density_q32 in [0, 2^32] is the noise density times 2^32, mean_q16 >= 65536 the mean
+ *   span length times 65536, E = 1 if eos_id >= 0, else 0.
+ *   Counts: L < 2 gives N = S = 0 and M = L. Otherwise the row has
+ *     N = clamp((L density_q32 + 2^31) >> 32, 1, L - 1) noise tokens, M = L - N kept tokens and
+ *     S = clamp((2 N 65536 + mean_q16) / (2 mean_q16), 1, min(N, M)) spans (integer division);
+ *   in_len = M + S + E and tgt_len = N + S + E. This is the arithmetic of T5's random_spans_noise_mask with
+ *   round-half-up where Python's round() rounds half to even (a deliberate difference, as is the
+ *   generator: T5 shuffles with its framework's, this draws keys with Philox).
+ *   Draws: boundary j, 1 <= j < max(N, M), of row r has x0..x3 = Philox4x32-10 of the element index
+ *   e = elem_base + r width + j, with ak_ids_mlm's counter and key layout (stream_id, seed). x0 is j's
+ *   key in the noise segmentation (used for j < N), x1 its key in the non-noise one (j < M). In each
+ *   segmentation the cuts are the S - 1 values of j with the smallest (key, j) pairs in lexicographic
+ *   order (equal keys: the smaller j first): a uniformly random composition into S non-empty parts.
+ *   Sorted, the noise cuts are a_1 < ... < a_(S-1) with a_0 = 0 and a_S = N; the others b_i, b_S = M.
+ *   Layout: the row reads segment 0, span 0, segment 1, span 1, ...: it begins with kept tokens and ends
+ *   with noise, as T5's does. Kept item v of segment i (b_i <= v < b_(i+1)) is column v + a_i; noise item
+ *   u of span i (a_i <= u < a_(i+1)) is column u + b_(i+1). sentinel(i) = sentinel_first + i
+ *   sentinel_step in wrapping int32 arithmetic (T5: the last vocabulary id and -1; sentinel_step = 0 with
+ *   sentinel_first = <mask>: one <mask> per span, BART's text infilling).
+ *   inputs  [rows x in_width], in's type:  inputs[r, v + i] = in[r, v + a_i]; inputs[r, b_(i+1) + i] =
+ *           sentinel(i); inputs[r, M + S] = eos_id if E; pad_id from in_len on.
+ *   targets [rows x tgt_width], in's type: targets[r, a_i + i] = sentinel(i); targets[r, u + i + 1] =
+ *           in[r, u + b_(i+1)]; targets[r, N + S] = eos_id if E; tgt_pad_id from tgt_len on.
+ *           L < 2 follows from N = S = 0: inputs hold the row's ids, then eos; targets eos alone.
+ *   in_lengths / tgt_lengths (optional, int32 [rows]): in_len and tgt_len, what the row needs even where
+ *           a width is shorter. noise (optional, u8 [rows x width]): 1 on noise columns, 0 on all others,
+ *           those from L on included.
+ * Ids travel at their full width (int64 ids outside int32 pass through); eos_id, the pads and the
+ * sentinels are int32 values. Nothing is stored at or past column in_width / tgt_width of a row (an
+ * element whose destination lies there is dropped) nor at or past row cap_rows. rows == 0 or cap_rows == 0
+ * launches nothing. Calls over parts of one batch draw what one call over the whole batch draws when
+ * elem_base is the part's first row times width. ak_ids_spans_lengths is the host arithmetic: out =
+ * {N, S, in_len, tgt_len} for a row of L ids.
+ * AK_ERR_ARG, on the host before any device work: NULL in, inputs or targets with rows > 0; width,
+ * in_width or tgt_width == 0; width > AK_SPANS_MAX_WIDTH; density_q32 > 2^32; mean_q16 < 65536; a flag bit
+ * other than AK_DENSE_I64; an output equal to in, to lengths or to another output; rows x the largest of
+ * the three widths out of range; ak_ids_spans_lengths: NULL out, or the same two bounds. */
+#define AK_SPANS_MAX_WIDTH 4096
+int ak_ids_spans(const void *in, const int32_t *lengths /*optional*/, uint64_t rows, uint32_t width, uint64_t seed,
+                 uint64_t stream_id, uint64_t elem_base, uint64_t density_q32, uint32_t mean_q16,
+                 int32_t sentinel_first, int32_t sentinel_step, int32_t eos_id, int32_t pad_id, int32_t tgt_pad_id,
+                 int flags, void *inputs, uint32_t in_width, void *targets, uint32_t tgt_width,
+                 int32_t *in_lengths /*optional*/, int32_t *tgt_lengths /*optional*/, uint8_t *noise /*optional*/,
+                 uint64_t cap_rows, void *stream);
+int ak_ids_spans_lengths(uint32_t L, uint64_t density_q32, uint32_t mean_q16, int has_eos, uint64_t out[4]);
+
 /* Always-sufficient output capacities (elements) for n rows of total_bytes input bytes.
  * ak_bpe_encode_cap holds for flags 2 / 3; with clean_hinglish=False (flags 0 / 1) NFKC can
  * expand a char (U+FDFA: 3 bytes -> 18 code points): AK_BPE_NFKC_EXPANSION * total_bytes + 2n + 16. */
